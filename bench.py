@@ -13,6 +13,12 @@ sized to not be the bottleneck.
   python bench.py --gpus 1 --steps 3 --warmup 1            # single GPU
   torchrun --nproc-per-node 8 bench.py --gpus 8 ...        # driver form
 
+A plain run sets up, warms up, times the steps and prints the result line;
+nothing else. --dump-outputs DIR additionally saves what the last timed
+step delivered (see dump_outputs). --full is where measurements beyond the
+headline figure live; today that is the per-stage timing report on stderr
+(also switched on by MODELX_BENCH_DEBUG=1).
+
 Rank 0 prints exactly one JSON line with the whole-job aggregate.
 """
 import argparse
@@ -56,6 +62,19 @@ def parse_args():
                         "and blob (no collectives). auto = fanout when world>1.")
     p.add_argument("--chunk-mib", type=int, default=256,
                    help="fan-out broadcast pipeline chunk (MiB)")
+    p.add_argument("--seed", type=int, default=0,
+                   help="payload RNG seed; rank r draws from stream seed + r, so "
+                        "the ranks of one job differ (seeds of different jobs "
+                        "that are less than the world size apart share "
+                        "streams). Same arguments, same payload bytes in every "
+                        "step of every run")
+    p.add_argument("--dump-outputs", default="", metavar="DIR",
+                   help="after the timed steps, write what the last timed step "
+                        "delivered as DIR/<name>.npy (float32, at most 64 MB "
+                        "over all ranks)")
+    p.add_argument("--full", action="store_true",
+                   help="everything beyond the headline figure: the per-step / "
+                        "per-stage timing report on stderr")
     return p.parse_args()
 
 
@@ -105,6 +124,56 @@ def cpu_smoke(args):
         shutil.rmtree(work, ignore_errors=True)
 
 
+DUMP_SAMPLE = 4 << 20  # most bytes sampled per pulled tensor (16 MiB as float32)
+DUMP_BUDGET = 60_000_000  # bytes of samples a whole job may write, all ranks
+#                           together; digests and .npy headers fit in the
+#                           4 MB left below the 64 MB limit
+
+
+def dump_sample_len(world, n_tensors):
+    """Elements sampled per pulled tensor: DUMP_SAMPLE, cut down so that
+    world ranks x n_tensors tensors x 4 bytes stay within DUMP_BUDGET."""
+    return min(DUMP_SAMPLE, DUMP_BUDGET // (4 * world * max(n_tensors, 1)))
+
+
+def dump_sample_indices(numel, k):
+    """The k sorted positions sampled from a tensor of numel > k elements: a
+    PCG64 stream seeded with numel, so two builds sample the same bytes."""
+    import numpy as np
+
+    return np.sort(np.random.Generator(np.random.PCG64(numel))
+                   .integers(0, numel, k, dtype=np.int64))
+
+
+def dump_outputs(out_dir, rank, world, manifests, pulled):
+    """Write what the last timed step handed its caller, as float32 .npy.
+
+    pulled: {name: uint8 tensor} from the step's pull(s) -> <name>.npy: the
+    bytes themselves, or for tensors above dump_sample_len() elements the
+    fixed sample at dump_sample_indices(). manifests: {payload name: Manifest}
+    from the step's push -> <name>.digest.npy: the payload blob's digest
+    string as character codes. Multi-rank runs prefix each file with
+    rank<r>. (every rank pulls the same number of tensors, so the per-tensor
+    share of DUMP_BUDGET is the same everywhere); the files of all ranks
+    together stay below 64 MB."""
+    import numpy as np
+    import torch
+
+    os.makedirs(out_dir, exist_ok=True)
+    prefix = f"rank{rank}." if world > 1 else ""
+    k = dump_sample_len(world, len(pulled))
+    for name, t in sorted(pulled.items()):
+        t = t.reshape(-1)
+        if t.numel() > k:
+            t = t[torch.from_numpy(dump_sample_indices(t.numel(), k)).to(t.device)]
+        np.save(os.path.join(out_dir, f"{prefix}{name}.npy"),
+                t.cpu().numpy().astype(np.float32))
+    for name, m in sorted(manifests.items()):
+        (digest,) = [b.digest for b in m.blobs if b.name == name]
+        np.save(os.path.join(out_dir, f"{prefix}{name}.digest.npy"),
+                np.asarray([ord(c) for c in digest], dtype=np.float32))
+
+
 class _CpuBenchClient:
     """Transfer-client stand-in for MODELX_BENCH_CPU dry-runs: same call
     surface as GpuClient for the bench loop, CPU bytes through the normal
@@ -128,8 +197,9 @@ class _CpuBenchClient:
         for name, t in tensors.items():
             with open(os.path.join(d, name), "wb") as f:
                 f.write(t.numpy().tobytes())
-        self._client.push(repository, version, d, quiet=True)
+        manifest = self._client.push(repository, version, d, quiet=True)
         shutil.rmtree(d, ignore_errors=True)
+        return manifest
 
     def pull_to_gpu(self, repository, version, verify=True):
         import tempfile
@@ -275,8 +345,15 @@ def main():
         repo = f"bench/rank{rank}"
     src = torch.empty(shard_bytes, dtype=torch.uint8,
                       device="cpu" if cpu_mode else f"cuda:{device}")
+    # every payload comes from src.random_ on this (per-rank) stream
+    torch.manual_seed(args.seed + rank)
 
     substeps = []
+    # --dump-outputs: what the LAST timed step returned (push manifests,
+    # pulled tensors), held past the timed region; nothing is kept otherwise
+    keep_last = bool(args.dump_outputs)
+    last_manifests, last_pulled = {}, {}
+    last_idx = args.steps - 1
 
     def one_step(step_idx: int):
         # fresh random payload → no HEAD-dedup shortcut; new digest every step
@@ -290,8 +367,10 @@ def main():
 
             from modelx_amd.client.fanout import fanout_pull_broadcast
 
-            g.push_from_gpu(repo, f"s{step_idx}-r{rank}", {"shard.bin": src},
-                            part_bytes=args.part_mib << 20)
+            m = g.push_from_gpu(repo, f"s{step_idx}-r{rank}", {"shard.bin": src},
+                                part_bytes=args.part_mib << 20)
+            if keep_last and step_idx == last_idx:
+                last_manifests["shard.bin"] = m
             dist.barrier()  # every shard published before the fan-out
             t2 = time.monotonic()
             landed = 0
@@ -300,6 +379,8 @@ def main():
                                             device, chunk=args.chunk_mib << 20,
                                             src_rank=r, verify=True)
                 landed += sum(t.numel() for t in out.values())
+                if keep_last and step_idx == last_idx:
+                    last_pulled.update({f"src{r}.{n}": t for n, t in out.items()})
                 del out
             assert landed == blob_bytes, (landed, blob_bytes)
             t3 = time.monotonic()
@@ -309,11 +390,15 @@ def main():
             dist.barrier()  # delete done before the next step's push
             t4 = time.monotonic()
         else:
-            g.push_from_gpu(repo, f"s{step_idx}", {"blob.bin": src},
-                            part_bytes=args.part_mib << 20)
+            m = g.push_from_gpu(repo, f"s{step_idx}", {"blob.bin": src},
+                                part_bytes=args.part_mib << 20)
             t2 = time.monotonic()
-            g.pull_to_gpu(repo, f"s{step_idx}", verify=True)  # GPU digest verify
+            out = g.pull_to_gpu(repo, f"s{step_idx}", verify=True)  # GPU digest verify
             t3 = time.monotonic()
+            if keep_last and step_idx == last_idx:
+                last_manifests["blob.bin"] = m
+                last_pulled.update(out)
+            del out
             # drop this step's objects so tmpfs doesn't fill across steps
             g.remote.delete_index(repo)
             t4 = time.monotonic()
@@ -346,8 +431,10 @@ def main():
                 torch.cuda.synchronize(device)
 
         def push(k):
-            g.push_from_gpu(repo, f"s{k}", {"blob.bin": src},
-                            part_bytes=args.part_mib << 20)
+            m = g.push_from_gpu(repo, f"s{k}", {"blob.bin": src},
+                                part_bytes=args.part_mib << 20)
+            if keep_last and k == last_idx:
+                last_manifests["blob.bin"] = m
 
         def clean(k):
             # NEVER concurrent with a push: blobs upload before their
@@ -365,7 +452,10 @@ def main():
             g.pull_to_gpu(repo, f"s{k - 1}", verify=True)
             th.join()
             clean(k - 1)
-        g.pull_to_gpu(repo, f"s{args.steps - 1}", verify=True)
+        out = g.pull_to_gpu(repo, f"s{args.steps - 1}", verify=True)
+        if keep_last:
+            last_pulled.update(out)
+        del out
         clean(args.steps - 1)
 
     def pipelined_fanout_steps():
@@ -388,8 +478,10 @@ def main():
                 torch.cuda.synchronize(device)
 
         def push(k):
-            g.push_from_gpu(repo, f"s{k}-r{rank}", {"shard.bin": src},
-                            part_bytes=args.part_mib << 20)
+            m = g.push_from_gpu(repo, f"s{k}-r{rank}", {"shard.bin": src},
+                                part_bytes=args.part_mib << 20)
+            if keep_last and k == last_idx:
+                last_manifests["shard.bin"] = m
 
         def fan(k):
             landed = 0
@@ -398,6 +490,8 @@ def main():
                                             chunk=args.chunk_mib << 20,
                                             src_rank=r, verify=True)
                 landed += sum(t.numel() for t in out.values())
+                if keep_last and k == last_idx:
+                    last_pulled.update({f"src{r}.{n}": t for n, t in out.items()})
                 del out
             assert landed == blob_bytes, (landed, blob_bytes)
 
@@ -450,7 +544,11 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
 
-    if os.environ.get("MODELX_BENCH_DEBUG") and rank == 0:
+    if keep_last:
+        dump_outputs(args.dump_outputs, rank, world, last_manifests, last_pulled)
+        last_pulled.clear()
+
+    if (args.full or os.environ.get("MODELX_BENCH_DEBUG")) and rank == 0:
         for i, (tg, tp, tl, td) in enumerate(substeps):
             print(f"# step {i}: gen={tg * 1e3:.0f}ms push={tp * 1e3:.0f}ms "
                   f"pull={tl * 1e3:.0f}ms delete={td * 1e3:.0f}ms", file=sys.stderr)
