@@ -17,6 +17,8 @@
 
 #include <cstdint>
 
+#include "modelx/device_abi.hpp"
+
 namespace {
 
 typedef uint8_t u8;

@@ -25,6 +25,10 @@
 
 #include <cstdint>
 
+#include "modelx/device_abi.hpp"
+
+using modelx::abi::ChunkLeavesDesc;
+
 #define DEV __device__ __forceinline__
 
 namespace {
@@ -170,15 +174,6 @@ __global__ __launch_bounds__(kBlockThreads) void sha256_chunk_leaves_kernel(
 // stream — the measured config-5 verify wall); the combined grid puts every
 // blob's chunks in flight at once. Buffers are located by binary search
 // over the chunk-prefix array in the descriptors.
-struct ChunkLeavesDesc {
-  const uint8_t* data;
-  uint8_t* leaves;
-  uint64_t total;
-  uint64_t chunk_size;
-  uint32_t chunk_base;  // chunks in all preceding buffers
-  uint32_t pad_;
-};
-
 __global__ __launch_bounds__(kBlockThreads) void sha256_chunk_leaves_many_kernel(
     const ChunkLeavesDesc* __restrict__ descs, uint32_t nbuf, uint32_t total_chunks) {
   __shared__ uint32_t lds_tail[kBlockThreads * kTailDwords];
@@ -261,12 +256,12 @@ hipError_t modelx_sha256_chunk_leaves(const void* data, uint64_t total, uint64_t
   return hipGetLastError();
 }
 
-hipError_t modelx_sha256_chunk_leaves_many(const void* descs_dev, uint32_t nbuf,
+hipError_t modelx_sha256_chunk_leaves_many(const ChunkLeavesDesc* descs_dev, uint32_t nbuf,
                                            uint32_t total_chunks, hipStream_t stream) {
   if (total_chunks == 0 || nbuf == 0) return hipSuccess;
   dim3 grid((total_chunks + kBlockThreads - 1) / kBlockThreads);
   hipLaunchKernelGGL(sha256_chunk_leaves_many_kernel, grid, dim3(kBlockThreads), 0, stream,
-                     static_cast<const ChunkLeavesDesc*>(descs_dev), nbuf, total_chunks);
+                     descs_dev, nbuf, total_chunks);
   return hipGetLastError();
 }
 

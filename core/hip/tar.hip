@@ -11,15 +11,12 @@
 
 #include <cstdint>
 
-namespace {
+#include "modelx/device_abi.hpp"
 
-struct TarEntry {
-  uint64_t header_off;   // offset of the 512 B header block
-  uint64_t payload_off;  // offset of file data
-  uint64_t size;         // file size in bytes
-  uint32_t typeflag;     // '0'/'\0' regular, '5' dir, 'L' GNU longname, ...
-  uint32_t mode;         // octal-decoded
-};
+using modelx::abi::CopySeg;
+using modelx::abi::TarEntry;
+
+namespace {
 
 __device__ uint64_t parse_octal(const uint8_t* p, int n) {
   uint64_t v = 0;
@@ -65,15 +62,9 @@ __global__ void tar_index_kernel(const uint8_t* __restrict__ tar, uint64_t tar_l
   *count = n;
 }
 
-// Scatter segments: seg i copies src[src_off..src_off+len) -> dst_ptr.
-struct CopySeg {
-  uint64_t src_off;
-  uint64_t dst_ptr;  // device address
-  uint64_t len;
-};
-
 constexpr int kScatterThreads = 256;
 
+// Scatter segments: seg i copies src[src_off..src_off+len) -> dst_ptr.
 __global__ __launch_bounds__(kScatterThreads) void tar_scatter_kernel(
     const uint8_t* __restrict__ tar, const CopySeg* __restrict__ segs, uint32_t nsegs) {
   uint32_t seg_idx = blockIdx.x;
@@ -104,20 +95,20 @@ __global__ __launch_bounds__(kScatterThreads) void tar_scatter_kernel(
 
 extern "C" {
 
-hipError_t modelx_tar_index(const void* tar, uint64_t tar_len, void* entries,
+hipError_t modelx_tar_index(const void* tar, uint64_t tar_len, TarEntry* entries,
                             uint32_t max_entries, uint32_t* count_dev, uint32_t* error_dev,
                             hipStream_t stream) {
   hipLaunchKernelGGL(tar_index_kernel, dim3(1), dim3(64), 0, stream,
                      static_cast<const uint8_t*>(tar), tar_len,
-                     static_cast<TarEntry*>(entries), max_entries, count_dev, error_dev);
+                     entries, max_entries, count_dev, error_dev);
   return hipGetLastError();
 }
 
-hipError_t modelx_tar_scatter(const void* tar, const void* segs, uint32_t nsegs,
+hipError_t modelx_tar_scatter(const void* tar, const CopySeg* segs, uint32_t nsegs,
                               hipStream_t stream) {
   if (nsegs == 0) return hipSuccess;
   hipLaunchKernelGGL(tar_scatter_kernel, dim3(nsegs), dim3(kScatterThreads), 0, stream,
-                     static_cast<const uint8_t*>(tar), static_cast<const CopySeg*>(segs), nsegs);
+                     static_cast<const uint8_t*>(tar), segs, nsegs);
   return hipGetLastError();
 }
 

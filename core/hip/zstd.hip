@@ -16,14 +16,12 @@
 // GPU decompression at all.
 #include <hip/hip_runtime.h>
 
+#include "modelx/device_abi.hpp"
 #include "modelx/zstd_core.hpp"
 #include "modelx/zstd_enc.hpp"
 
 using namespace modelx::zstd;
-
-struct MxzFrameC {
-  uint64_t c_off, c_size, d_off, d_size;
-};
+using modelx::zstdhost::SeekEntry;
 
 // ----------------------------------------------------------- decompress ----
 
@@ -31,27 +29,27 @@ struct MxzFrameC {
 // barrier counts line up, and the lane-strided copies go 4x wider — the
 // win on raw-literal frames (our encoder's output), which are copy-bound.
 __global__ __launch_bounds__(256) void zstd_decompress_frames_kernel(
-    const u8* __restrict__ src, const MxzFrameC* __restrict__ frames, u32 nframes,
+    const u8* __restrict__ src, const SeekEntry* __restrict__ frames, u32 nframes,
     u8* __restrict__ dst, u8* __restrict__ lit_scratch, i64* __restrict__ rc, u32 flags) {
   __shared__ DecCtx ctx;
   u32 f = blockIdx.x;
   if (f >= nframes) return;
   ctx.flags = flags;
   ctx.lit_scratch = lit_scratch + (u64)f * kBlockMax;
-  MxzFrameC fr = frames[f];
+  SeekEntry fr = frames[f];
   i64 n = decode_frame(src + fr.c_off, fr.c_size, dst + fr.d_off, fr.d_size, &ctx, nullptr);
   if (threadIdx.x == 0) rc[f] = (n == (i64)fr.d_size) ? 0 : (n < 0 ? n : MXZ_ERR_CORRUPT);
 }
 
-extern "C" hipError_t modelx_zstd_decompress_frames(const void* src, const void* frames_dev,
+extern "C" hipError_t modelx_zstd_decompress_frames(const void* src,
+                                                    const SeekEntry* frames_dev,
                                                     uint32_t nframes, void* dst,
                                                     void* lit_scratch, int64_t* rc_dev,
                                                     uint32_t flags, hipStream_t stream) {
   if (nframes == 0) return hipSuccess;
   hipLaunchKernelGGL(zstd_decompress_frames_kernel, dim3(nframes), dim3(256), 0, stream,
-                     static_cast<const u8*>(src), static_cast<const MxzFrameC*>(frames_dev),
-                     nframes, static_cast<u8*>(dst), static_cast<u8*>(lit_scratch), rc_dev,
-                     flags);
+                     static_cast<const u8*>(src), frames_dev, nframes, static_cast<u8*>(dst),
+                     static_cast<u8*>(lit_scratch), rc_dev, flags);
   return hipGetLastError();
 }
 

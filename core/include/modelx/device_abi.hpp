@@ -1,0 +1,78 @@
+// The host<->kernel ABI, declared once: the POD structs that cross the
+// launch boundary in device memory and the extern "C" launchers of
+// core/hip/*.hip. Each .hip file includes this header, so the compiler checks
+// every launcher definition against the prototype the engine calls. The
+// decode kernel's frame descriptor is zstdhost::SeekEntry itself: the engine
+// uploads the parsed seek table as-is.
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+
+#include "modelx/zstd_host.hpp"
+
+namespace modelx {
+namespace abi {
+
+struct TarEntry {
+  uint64_t header_off;   // offset of the 512 B header block
+  uint64_t payload_off;  // offset of file data
+  uint64_t size;         // file size in bytes
+  uint32_t typeflag;     // '0'/'\0' regular, '5' dir, 'L' GNU longname, ...
+  uint32_t mode;         // octal-decoded
+};
+
+// Scatter segment: copies src[src_off..src_off+len) -> dst_ptr.
+struct CopySeg {
+  uint64_t src_off;
+  uint64_t dst_ptr;  // device address
+  uint64_t len;
+};
+
+struct ChunkLeavesDesc {
+  const uint8_t* data;
+  uint8_t* leaves;
+  uint64_t total;
+  uint64_t chunk_size;
+  uint32_t chunk_base;  // chunks in all preceding buffers
+  uint32_t pad_;
+};
+
+}  // namespace abi
+}  // namespace modelx
+
+extern "C" {
+
+hipError_t modelx_sha256_chunk_leaves(const void* data, uint64_t total, uint64_t chunk_size,
+                                      void* leaves, uint32_t nchunks, hipStream_t stream);
+hipError_t modelx_sha256_chunk_leaves_many(const modelx::abi::ChunkLeavesDesc* descs_dev,
+                                           uint32_t nbuf, uint32_t total_chunks,
+                                           hipStream_t stream);
+hipError_t modelx_sha256_multibuf(const void* const* buffers, const uint64_t* lengths,
+                                  uint32_t nbuf, void* digests, hipStream_t stream);
+hipError_t modelx_tar_index(const void* tar, uint64_t tar_len, modelx::abi::TarEntry* entries,
+                            uint32_t max_entries, uint32_t* count_dev, uint32_t* error_dev,
+                            hipStream_t stream);
+hipError_t modelx_tar_scatter(const void* tar, const modelx::abi::CopySeg* segs, uint32_t nsegs,
+                              hipStream_t stream);
+hipError_t modelx_zstd_decompress_frames(const void* src,
+                                         const modelx::zstdhost::SeekEntry* frames_dev,
+                                         uint32_t nframes, void* dst, void* lit_scratch,
+                                         int64_t* rc_dev, uint32_t flags, hipStream_t stream);
+hipError_t modelx_zstd_compress_frames(const void* src, uint64_t srclen, uint32_t frame_raw,
+                                       uint32_t first_frame, uint32_t nframes, void* dst_scratch,
+                                       uint64_t stride, void* seq_scratch, uint32_t max_seqs,
+                                       int64_t* out_sizes_dev, uint32_t flags,
+                                       hipStream_t stream);
+hipError_t modelx_dedup_insert(const void* leaves_dev, uint32_t nchunks, uint64_t base,
+                               uint64_t chunk_size, uint64_t total, void* table, uint64_t cap,
+                               uint32_t* dropped_dev, hipStream_t stream);
+hipError_t modelx_dedup_probe(const void* leaves_dev, uint32_t nchunks, uint64_t chunk_size,
+                              uint64_t total, const void* table, uint64_t cap,
+                              uint64_t* src_addr_dev, uint64_t* src_len_dev, hipStream_t stream);
+hipError_t modelx_dedup_gather(const uint64_t* src_addr_dev, const uint64_t* src_len_dev,
+                               uint32_t nchunks, uint64_t dst_base, uint64_t chunk_size,
+                               hipStream_t stream);
+
+}  // extern "C"

@@ -19,8 +19,28 @@ struct SeekEntry {
   uint64_t d_off, d_size;  // decompressed span
 };
 
+// The seek-table format, in two strict steps over host bytes: a caller whose
+// blob lives elsewhere (the GPU engine) fetches the fixed-size footer, learns
+// the table's length from it, then fetches exactly that tail. Both steps throw
+// std::runtime_error on malformed input.
+constexpr size_t kSeekFooterBytes = 17;
+
+struct SeekFooter {
+  uint32_t nframes;
+  uint32_t entry_bytes;  // 8, or 12 with per-frame checksums
+  uint64_t table_bytes;  // whole skippable frame: 8 + nframes*entry_bytes + 9
+};
+
+// tail17 = the blob's last kSeekFooterBytes (unread if blob_len is shorter).
+SeekFooter parse_seek_footer(const uint8_t* tail17, uint64_t blob_len);
+
+// table = the blob's last f.table_bytes. Appends one entry per frame to *out
+// and returns the decompressed total.
+uint64_t parse_seek_entries(const uint8_t* table, const SeekFooter& f, uint64_t blob_len,
+                            std::vector<SeekEntry>* out);
+
 // Parse the seek table from a full blob. Returns empty vector if the blob
-// has no seekable footer (caller falls back to sequential frame walking).
+// has no valid seek table (caller falls back to sequential frame walking).
 std::vector<SeekEntry> parse_seek_table(const uint8_t* blob, size_t len);
 
 // Walk frames sequentially (no seek table needed); returns entries or empty

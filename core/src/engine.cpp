@@ -39,62 +39,17 @@
 #include <thread>
 #include <vector>
 
+#include "modelx/device_abi.hpp"
 #include "modelx/http.hpp"
 #include "modelx/zstd_core.hpp"
 #include "modelx/zstd_host.hpp"
 
 namespace py = pybind11;
 using namespace modelx;
-
-extern "C" hipError_t modelx_sha256_chunk_leaves(const void* data, uint64_t total,
-                                                 uint64_t chunk_size, void* leaves,
-                                                 uint32_t nchunks, hipStream_t stream);
-extern "C" hipError_t modelx_sha256_multibuf(const void* const* buffers, const uint64_t* lengths,
-                                             uint32_t nbuf, void* digests, hipStream_t stream);
-extern "C" hipError_t modelx_sha256_chunk_leaves_many(const void* descs_dev, uint32_t nbuf,
-                                                      uint32_t total_chunks,
-                                                      hipStream_t stream);
-
-// host mirror of sha256.hip ChunkLeavesDesc
-struct ChunkLeavesDescHost {
-  const void* data;
-  void* leaves;
-  uint64_t total;
-  uint64_t chunk_size;
-  uint32_t chunk_base;
-  uint32_t pad_;
-};
-extern "C" hipError_t modelx_tar_index(const void* tar, uint64_t tar_len, void* entries,
-                                       uint32_t max_entries, uint32_t* count_dev,
-                                       uint32_t* error_dev, hipStream_t stream);
-extern "C" hipError_t modelx_tar_scatter(const void* tar, const void* segs, uint32_t nsegs,
-                                         hipStream_t stream);
-extern "C" hipError_t modelx_zstd_decompress_frames(const void* src, const void* frames_dev,
-                                                    uint32_t nframes, void* dst,
-                                                    void* lit_scratch, int64_t* rc_dev,
-                                                    uint32_t flags, hipStream_t stream);
-extern "C" hipError_t modelx_dedup_insert(const void* leaves_dev, uint32_t nchunks,
-                                           uint64_t base, uint64_t chunk_size, uint64_t total,
-                                           void* table, uint64_t cap, uint32_t* dropped_dev,
-                                           hipStream_t stream);
-extern "C" hipError_t modelx_dedup_probe(const void* leaves_dev, uint32_t nchunks,
-                                         uint64_t chunk_size, uint64_t total, const void* table,
-                                         uint64_t cap, uint64_t* src_addr_dev,
-                                         uint64_t* src_len_dev, hipStream_t stream);
-extern "C" hipError_t modelx_dedup_gather(const uint64_t* src_addr_dev,
-                                          const uint64_t* src_len_dev, uint32_t nchunks,
-                                          uint64_t dst_base, uint64_t chunk_size,
-                                          hipStream_t stream);
-extern "C" hipError_t modelx_zstd_compress_frames(const void* src, uint64_t srclen,
-                                                  uint32_t frame_raw, uint32_t first_frame,
-                                                  uint32_t nframes, void* dst_scratch,
-                                                  uint64_t stride, void* seq_scratch,
-                                                  uint32_t max_seqs, int64_t* out_sizes_dev,
-                                                  uint32_t flags, hipStream_t stream);
-
-struct MxzFrameHost {
-  uint64_t c_off, c_size, d_off, d_size;
-};
+using modelx::abi::ChunkLeavesDesc;
+using modelx::abi::CopySeg;
+using modelx::abi::TarEntry;
+using zstdhost::SeekEntry;
 
 // MODELX_ZSTD_FLAGS: bit0 disables the lane-parallel huffman encoder,
 // bit1 disables the wave-split literal-stream decoder (bisection/panic
@@ -106,14 +61,6 @@ static uint32_t zstd_flags() {
   }();
   return f;
 }
-
-struct TarEntryHost {
-  uint64_t header_off, payload_off, size;
-  uint32_t typeflag, mode;
-};
-struct CopySegHost {
-  uint64_t src_off, dst_ptr, len;
-};
 
 #define HIP_CHECK(expr)                                                                 \
   do {                                                                                  \
@@ -139,6 +86,50 @@ struct Slot {
 struct Range {
   uint64_t offset;
   uint64_t length;
+};
+
+// Owner of one hipMalloc'd allocation (move-only); the only place device
+// memory is freed. Used directly for per-call temporaries.
+class DeviceBuffer {
+ public:
+  DeviceBuffer() = default;
+  explicit DeviceBuffer(size_t bytes) { HIP_CHECK(hipMalloc(&p_, bytes)); }
+  DeviceBuffer(DeviceBuffer&& o) noexcept : p_(o.p_) { o.p_ = nullptr; }
+  DeviceBuffer& operator=(DeviceBuffer&& o) noexcept {
+    std::swap(p_, o.p_);
+    return *this;
+  }
+  ~DeviceBuffer() {
+    if (p_) hipFree(p_);
+  }
+  template <class T = void>
+  T* get() const { return static_cast<T*>(p_); }
+  explicit operator bool() const { return p_ != nullptr; }
+
+ private:
+  void* p_ = nullptr;
+};
+
+// Grow-only device scratch kept across calls: per-call hipMalloc/hipFree of
+// GiB-scale scratch dominated concurrent decompress (config-5 profile)
+// before this. reserve() reallocates only when the request outgrows the
+// capacity (contents are not carried over) and returns the buffer.
+class DeviceScratch {
+ public:
+  template <class T = void>
+  T* reserve(size_t bytes) {
+    if (cap_ < bytes) {
+      cap_ = 0;
+      buf_ = DeviceBuffer();  // free first: old and new never coexist
+      buf_ = DeviceBuffer(bytes);
+      cap_ = bytes;
+    }
+    return buf_.get<T>();
+  }
+
+ private:
+  DeviceBuffer buf_;
+  size_t cap_ = 0;
 };
 
 // Keep-alive connection pool: checkout/checkin per (host,port). Reused
@@ -184,17 +175,13 @@ class GpuEngine {
     streams_.resize(num_streams);
     for (auto& st : streams_) HIP_CHECK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
     HIP_CHECK(hipStreamCreateWithFlags(&hash_stream_, hipStreamNonBlocking));
+    HIP_CHECK(hipEventCreateWithFlags(&zs_staged_, hipEventDisableTiming));
   }
 
   ~GpuEngine() {
-    if (dedup_table_) hipFree(dedup_table_);
-    if (dedup_dropped_) hipFree(dedup_dropped_);
-    for (auto& p : ds_ptr_)
-      if (p) hipFree(p);
-    for (auto& p : zs_ptr_)
-      if (p) hipFree(p);
     for (auto& st : streams_) hipStreamDestroy(st);
     hipStreamDestroy(hash_stream_);
+    hipEventDestroy(zs_staged_);
     for (auto& s : slots_) {
       if (s.event) hipEventDestroy(s.event);
       if (s.host) hipHostFree(s.host);
@@ -251,13 +238,13 @@ class GpuEngine {
                      uint64_t size, uintptr_t dst_ptr, int num_conns, uint64_t base_offset,
                      uint64_t hash_chunk, std::string* leaves_out,
                      const std::vector<Range>* explicit_ranges) {
-    void* dleaves = nullptr;
+    DeviceBuffer dleaves;
     uint32_t total_chunks = 0;
     if (hash_chunk) {
       if (slot_bytes_ % hash_chunk != 0)
         throw std::runtime_error("slot_bytes must be a multiple of chunk_size");
       total_chunks = size ? static_cast<uint32_t>((size + hash_chunk - 1) / hash_chunk) : 1;
-      HIP_CHECK(hipMalloc(&dleaves, static_cast<size_t>(total_chunks) * 32));
+      dleaves = DeviceBuffer(static_cast<size_t>(total_chunks) * 32);
     }
     py::gil_scoped_release release;
     HIP_CHECK(hipSetDevice(device_));
@@ -313,7 +300,12 @@ class GpuEngine {
     std::atomic<int> stream_rr{0};
     for (int w = 0; w < num_conns; w++) {
       workers.emplace_back([&, w] {
-        HIP_CHECK(hipSetDevice(device_));
+        // no HIP_CHECK here: a throw out of a thread body is std::terminate
+        if (hipError_t e = hipSetDevice(device_); e != hipSuccess) {
+          std::lock_guard<std::mutex> lk(err_mu);
+          if (error.empty()) error = std::string("hip: ") + hipGetErrorString(e);
+          return;
+        }
         auto conn_holder = conn_pool_.checkout(u.host, u.port, u.scheme == "https");
         http::ClientConn& conn = *conn_holder;
         http::Headers h;
@@ -356,7 +348,7 @@ class GpuEngine {
                     static_cast<uint32_t>((plen + hash_chunk - 1) / hash_chunk);
                 e = modelx_sha256_chunk_leaves(
                     reinterpret_cast<char*>(dst_ptr) + abs_off, plen, hash_chunk,
-                    static_cast<char*>(dleaves) + static_cast<size_t>(first_chunk) * 32,
+                    dleaves.get<char>() + static_cast<size_t>(first_chunk) * 32,
                     n_chunks, st);
               }
               if (e == hipSuccess) e = hipEventRecord(slot->event, st);
@@ -398,9 +390,11 @@ class GpuEngine {
     for (auto& st : streams_) HIP_CHECK(hipStreamSynchronize(st));
     if (hash_chunk) {
       leaves_out->resize(static_cast<size_t>(total_chunks) * 32);
-      HIP_CHECK(hipMemcpy(&(*leaves_out)[0], dleaves, leaves_out->size(),
+      HIP_CHECK(hipMemcpy(&(*leaves_out)[0], dleaves.get(), leaves_out->size(),
                           hipMemcpyDeviceToHost));
-      hipFree(dleaves);
+      // released here on success, not at scope exit: hipFree waits for the
+      // device, and at scope exit the GIL is held again
+      dleaves = DeviceBuffer();
     }
     double t1 = now_s();
     {
@@ -422,17 +416,17 @@ class GpuEngine {
   py::bytes sha256_chunk_leaves(uintptr_t dev_ptr, uint64_t size, uint64_t chunk_size) {
     HIP_CHECK(hipSetDevice(device_));
     uint32_t nchunks = size ? static_cast<uint32_t>((size + chunk_size - 1) / chunk_size) : 1;
-    void* dleaves = nullptr;
-    HIP_CHECK(hipMalloc(&dleaves, static_cast<size_t>(nchunks) * 32));
     std::string out;
     {
+      // temporaries live inside the GIL-released block: hipFree waits for
+      // the device and must not do so holding the GIL
       py::gil_scoped_release release;
+      DeviceBuffer dleaves(static_cast<size_t>(nchunks) * 32);
       HIP_CHECK(modelx_sha256_chunk_leaves(reinterpret_cast<void*>(dev_ptr), size, chunk_size,
-                                           dleaves, nchunks, hash_stream_));
+                                           dleaves.get(), nchunks, hash_stream_));
       out.resize(static_cast<size_t>(nchunks) * 32);
       HIP_CHECK(hipStreamSynchronize(hash_stream_));
-      HIP_CHECK(hipMemcpy(&out[0], dleaves, out.size(), hipMemcpyDeviceToHost));
-      hipFree(dleaves);
+      HIP_CHECK(hipMemcpy(&out[0], dleaves.get(), out.size(), hipMemcpyDeviceToHost));
     }
     return py::bytes(out);
   }
@@ -448,32 +442,25 @@ class GpuEngine {
       hptrs[i] = reinterpret_cast<const void*>(bufs[i].first);
       hlens[i] = bufs[i].second;
     }
-    void* dptrs = nullptr;
-    void* dlens = nullptr;
-    void* ddig = nullptr;
-    HIP_CHECK(hipMalloc(&dptrs, n * sizeof(void*)));
-    HIP_CHECK(hipMalloc(&dlens, n * sizeof(uint64_t)));
-    HIP_CHECK(hipMalloc(&ddig, static_cast<size_t>(n) * 32));
     std::string out;
     {
       py::gil_scoped_release release;
+      DeviceBuffer dptrs(n * sizeof(void*));
+      DeviceBuffer dlens(n * sizeof(uint64_t));
+      DeviceBuffer ddig(static_cast<size_t>(n) * 32);
       // stream-ordered staging: a plain hipMemcpy is NOT ordered against a
       // kernel launched on a non-blocking stream — the kernel could read
       // stale parameters (observed as rare packed-frame corruption in the
       // equivalent zstd path)
-      HIP_CHECK(hipMemcpyAsync(dptrs, hptrs.data(), n * sizeof(void*),
+      HIP_CHECK(hipMemcpyAsync(dptrs.get(), hptrs.data(), n * sizeof(void*),
                                hipMemcpyHostToDevice, hash_stream_));
-      HIP_CHECK(hipMemcpyAsync(dlens, hlens.data(), n * sizeof(uint64_t),
+      HIP_CHECK(hipMemcpyAsync(dlens.get(), hlens.data(), n * sizeof(uint64_t),
                                hipMemcpyHostToDevice, hash_stream_));
-      HIP_CHECK(modelx_sha256_multibuf(reinterpret_cast<const void* const*>(dptrs),
-                                       reinterpret_cast<const uint64_t*>(dlens), n, ddig,
-                                       hash_stream_));
+      HIP_CHECK(modelx_sha256_multibuf(dptrs.get<const void*>(), dlens.get<uint64_t>(), n,
+                                       ddig.get(), hash_stream_));
       out.resize(static_cast<size_t>(n) * 32);
       HIP_CHECK(hipStreamSynchronize(hash_stream_));
-      HIP_CHECK(hipMemcpy(&out[0], ddig, out.size(), hipMemcpyDeviceToHost));
-      hipFree(dptrs);
-      hipFree(dlens);
-      hipFree(ddig);
+      HIP_CHECK(hipMemcpy(&out[0], ddig.get(), out.size(), hipMemcpyDeviceToHost));
     }
     return py::bytes(out);
   }
@@ -505,58 +492,19 @@ class GpuEngine {
     unsigned char md[32];
     {
       py::gil_scoped_release release;
-      EVP_MD_CTX* ctx = EVP_MD_CTX_new();
-      if (!ctx || EVP_DigestInit_ex(ctx, EVP_sha256(), nullptr) != 1) {
-        if (ctx) EVP_MD_CTX_free(ctx);
+      std::unique_ptr<EVP_MD_CTX, decltype(&EVP_MD_CTX_free)> ctx(EVP_MD_CTX_new(),
+                                                                  &EVP_MD_CTX_free);
+      if (!ctx || EVP_DigestInit_ex(ctx.get(), EVP_sha256(), nullptr) != 1)
         throw std::runtime_error("EVP sha256 init failed");
-      }
-      if (size) {
-        hipStream_t st_a = streams_[push_rr_.fetch_add(1) % streams_.size()];
-        hipStream_t st_b = streams_[push_rr_.fetch_add(1) % streams_.size()];
-        Slot* cur = nullptr;
-        Slot* nxt = nullptr;
-        {
-          std::unique_lock<std::mutex> lk(mu_);
-          cv_free_.wait(lk, [&] { return free_.size() >= 2; });
-          cur = free_.front();
-          free_.pop();
-          nxt = free_.front();
-          free_.pop();
-        }
-        uint64_t off = 0;
-        uint64_t cur_len = std::min<uint64_t>(slot_bytes_, size);
-        hipError_t e = hipMemcpyAsync(cur->host, reinterpret_cast<char*>(src_ptr), cur_len,
-                                      hipMemcpyDeviceToHost, st_a);
-        if (e == hipSuccess) e = hipEventRecord(cur->event, st_a);
-        while (e == hipSuccess && off < size) {
-          uint64_t next_off = off + cur_len;
-          uint64_t next_len =
-              next_off < size ? std::min<uint64_t>(slot_bytes_, size - next_off) : 0;
-          if (next_len) {
-            e = hipMemcpyAsync(nxt->host, reinterpret_cast<char*>(src_ptr) + next_off,
-                               next_len, hipMemcpyDeviceToHost, st_b);
-            if (e == hipSuccess) e = hipEventRecord(nxt->event, st_b);
-            if (e != hipSuccess) break;
-            std::swap(st_a, st_b);
-          }
-          e = hipEventSynchronize(cur->event);
-          if (e != hipSuccess) break;
-          EVP_DigestUpdate(ctx, cur->host, cur_len);
-          std::swap(cur, nxt);
-          off = next_off;
-          cur_len = next_len;
-        }
-        release_slot(cur);
-        release_slot(nxt);
-        if (e != hipSuccess) {
-          EVP_MD_CTX_free(ctx);
-          throw std::runtime_error(std::string("sha256_canonical_device: hip: ") +
-                                   hipGetErrorString(e));
-        }
-      }
+      hipError_t e = drain_device(src_ptr, size, [&](const char* p, uint64_t len) {
+        EVP_DigestUpdate(ctx.get(), p, len);
+        return true;
+      });
+      if (e != hipSuccess)
+        throw std::runtime_error(std::string("sha256_canonical_device: hip: ") +
+                                 hipGetErrorString(e));
       unsigned int mdlen = 0;
-      EVP_DigestFinal_ex(ctx, md, &mdlen);
-      EVP_MD_CTX_free(ctx);
+      EVP_DigestFinal_ex(ctx.get(), md, &mdlen);
     }
     return py::bytes(reinterpret_cast<char*>(md), 32);
   }
@@ -564,7 +512,9 @@ class GpuEngine {
   // -------------------------------------------------------------- push ----
 
   // Upload device memory [src_ptr, src_ptr+size) as the body of `method` to
-  // url (one part). Streams D2H through the pinned ring.
+  // url (one part). Streams D2H through the pinned ring. The pooled
+  // connection goes back to the pool only once the response has been read;
+  // every failure path simply drops it.
   py::dict push_part_from_device(const std::string& url, const std::string& method,
                                  const std::map<std::string, std::string>& headers,
                                  uintptr_t src_ptr, uint64_t size) {
@@ -578,58 +528,17 @@ class GpuEngine {
     for (auto& kv : headers) h[kv.first] = kv.second;
     if (!conn.send_request(method, u.target(), h, static_cast<int64_t>(size)))
       throw std::runtime_error("push: send_request failed");
-    // double-buffered D2H → send; streams chosen round-robin so concurrent
-    // part uploads don't serialize on one stream
-    hipStream_t st_a = streams_[push_rr_.fetch_add(1) % streams_.size()];
-    hipStream_t st_b = streams_[push_rr_.fetch_add(1) % streams_.size()];
-    // both slots in one wait: sequential acquire_slot() would hold-and-wait
-    // and can deadlock when >= num_slots pushes run concurrently
-    Slot* cur = nullptr;
-    Slot* nxt = nullptr;
-    {
-      std::unique_lock<std::mutex> lk(mu_);
-      cv_free_.wait(lk, [&] { return free_.size() >= 2; });
-      cur = free_.front();
-      free_.pop();
-      nxt = free_.front();
-      free_.pop();
-    }
-    uint64_t off = 0;
-    uint64_t cur_len = std::min<uint64_t>(slot_bytes_, size);
-    HIP_CHECK(hipMemcpyAsync(cur->host, reinterpret_cast<char*>(src_ptr), cur_len,
-                             hipMemcpyDeviceToHost, st_a));
-    HIP_CHECK(hipEventRecord(cur->event, st_a));
-    while (off < size) {
-      uint64_t next_off = off + cur_len;
-      uint64_t next_len = next_off < size ? std::min<uint64_t>(slot_bytes_, size - next_off) : 0;
-      if (next_len) {
-        HIP_CHECK(hipMemcpyAsync(nxt->host, reinterpret_cast<char*>(src_ptr) + next_off, next_len,
-                                 hipMemcpyDeviceToHost, st_b));
-        HIP_CHECK(hipEventRecord(nxt->event, st_b));
-        std::swap(st_a, st_b);
-      }
-      HIP_CHECK(hipEventSynchronize(cur->event));
-      if (!conn.send_body(cur->host, cur_len)) {
-        release_slot(cur);
-        release_slot(nxt);
-        throw std::runtime_error("push: send_body failed");
-      }
-      std::swap(cur, nxt);
-      off = next_off;
-      cur_len = next_len;
-    }
+    bool sent = true;
+    HIP_CHECK(drain_device(src_ptr, size, [&](const char* p, uint64_t len) {
+      return sent = conn.send_body(p, len);
+    }));
+    if (!sent) throw std::runtime_error("push: send_body failed");
     int status = 0;
     http::Headers rh;
-    if (!conn.read_response_head(&status, &rh)) {
-      release_slot(cur);
-      release_slot(nxt);
-      throw std::runtime_error("push: no response");
-    }
+    if (!conn.read_response_head(&status, &rh)) throw std::runtime_error("push: no response");
     char drain[4096];
     while (conn.read_body(drain, sizeof drain) > 0) {
     }
-    release_slot(cur);
-    release_slot(nxt);
     conn_pool_.checkin(std::move(conn_holder));
     double t1 = now_s();
     if (status < 200 || status >= 300)
@@ -651,50 +560,41 @@ class GpuEngine {
   py::list tar_index(uintptr_t tar_ptr, uint64_t tar_len) {
     HIP_CHECK(hipSetDevice(device_));
     uint32_t max_entries = 65536;
-    void* dentries = nullptr;
-    uint32_t* dcount = nullptr;
-    HIP_CHECK(hipMalloc(&dentries, max_entries * sizeof(TarEntryHost)));
-    HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&dcount), 2 * sizeof(uint32_t)));
-    std::vector<TarEntryHost> entries;
+    std::vector<TarEntry> entries;
     uint32_t count = 0, error = 0;
     {
       py::gil_scoped_release release;
-      HIP_CHECK(modelx_tar_index(reinterpret_cast<void*>(tar_ptr), tar_len, dentries,
-                                 max_entries, dcount, dcount + 1, hash_stream_));
+      DeviceBuffer dentries(max_entries * sizeof(TarEntry));
+      DeviceBuffer dcount_buf(2 * sizeof(uint32_t));
+      uint32_t* dcount = dcount_buf.get<uint32_t>();
+      HIP_CHECK(modelx_tar_index(reinterpret_cast<void*>(tar_ptr), tar_len,
+                                 dentries.get<TarEntry>(), max_entries, dcount, dcount + 1,
+                                 hash_stream_));
       HIP_CHECK(hipStreamSynchronize(hash_stream_));
       HIP_CHECK(hipMemcpy(&count, dcount, sizeof count, hipMemcpyDeviceToHost));
       HIP_CHECK(hipMemcpy(&error, dcount + 1, sizeof error, hipMemcpyDeviceToHost));
-      if (error) {
-        hipFree(dentries);
-        hipFree(dcount);
-        throw std::runtime_error("tar_index: malformed archive or too many entries");
-      }
+      if (error) throw std::runtime_error("tar_index: malformed archive or too many entries");
       entries.resize(count);
       if (count)
-        HIP_CHECK(hipMemcpy(entries.data(), dentries, count * sizeof(TarEntryHost),
+        HIP_CHECK(hipMemcpy(entries.data(), dentries.get(), count * sizeof(TarEntry),
                             hipMemcpyDeviceToHost));
-      hipFree(dentries);
-      hipFree(dcount);
     }
     // gather headers (+ longname payloads) to host in one shot
     std::string headers(static_cast<size_t>(count) * 512, '\0');
     if (count) {
       py::gil_scoped_release release;
-      void* dgather = nullptr;
-      HIP_CHECK(hipMalloc(&dgather, headers.size()));
-      std::vector<CopySegHost> segs(count);
+      DeviceBuffer dgather(headers.size());
+      std::vector<CopySeg> segs(count);
       for (uint32_t i = 0; i < count; i++)
-        segs[i] = {entries[i].header_off, reinterpret_cast<uint64_t>(dgather) + i * 512, 512};
-      void* dsegs = nullptr;
-      HIP_CHECK(hipMalloc(&dsegs, segs.size() * sizeof(CopySegHost)));
-      HIP_CHECK(hipMemcpyAsync(dsegs, segs.data(), segs.size() * sizeof(CopySegHost),
+        segs[i] = {entries[i].header_off, reinterpret_cast<uint64_t>(dgather.get()) + i * 512,
+                   512};
+      DeviceBuffer dsegs(segs.size() * sizeof(CopySeg));
+      HIP_CHECK(hipMemcpyAsync(dsegs.get(), segs.data(), segs.size() * sizeof(CopySeg),
                                hipMemcpyHostToDevice, hash_stream_));
-      HIP_CHECK(modelx_tar_scatter(reinterpret_cast<void*>(tar_ptr), dsegs, count,
-                                   hash_stream_));
+      HIP_CHECK(modelx_tar_scatter(reinterpret_cast<void*>(tar_ptr), dsegs.get<CopySeg>(),
+                                   count, hash_stream_));
       HIP_CHECK(hipStreamSynchronize(hash_stream_));
-      HIP_CHECK(hipMemcpy(&headers[0], dgather, headers.size(), hipMemcpyDeviceToHost));
-      hipFree(dsegs);
-      hipFree(dgather);
+      HIP_CHECK(hipMemcpy(&headers[0], dgather.get(), headers.size(), hipMemcpyDeviceToHost));
     }
     py::list out;
     std::string pending_longname;
@@ -762,21 +662,19 @@ class GpuEngine {
     if (segs.empty()) return;
     py::gil_scoped_release release;
     // split into <=4 MiB pieces for load balance across CUs
-    std::vector<CopySegHost> pieces;
+    std::vector<CopySeg> pieces;
     constexpr uint64_t kPiece = 4ull << 20;
     for (auto& t : segs) {
       uint64_t src_off = std::get<0>(t), dst = std::get<1>(t), len = std::get<2>(t);
       for (uint64_t off = 0; off < len; off += kPiece)
         pieces.push_back({src_off + off, dst + off, std::min(kPiece, len - off)});
     }
-    void* dsegs = nullptr;
-    HIP_CHECK(hipMalloc(&dsegs, pieces.size() * sizeof(CopySegHost)));
-    HIP_CHECK(hipMemcpyAsync(dsegs, pieces.data(), pieces.size() * sizeof(CopySegHost),
+    DeviceBuffer dsegs(pieces.size() * sizeof(CopySeg));
+    HIP_CHECK(hipMemcpyAsync(dsegs.get(), pieces.data(), pieces.size() * sizeof(CopySeg),
                              hipMemcpyHostToDevice, hash_stream_));
-    HIP_CHECK(modelx_tar_scatter(reinterpret_cast<void*>(tar_ptr), dsegs,
+    HIP_CHECK(modelx_tar_scatter(reinterpret_cast<void*>(tar_ptr), dsegs.get<CopySeg>(),
                                  static_cast<uint32_t>(pieces.size()), hash_stream_));
     HIP_CHECK(hipStreamSynchronize(hash_stream_));
-    hipFree(dsegs);
   }
 
   // ------------------------------------------------------------- zstd ----
@@ -786,31 +684,6 @@ class GpuEngine {
   // One workgroup per frame (core/hip/zstd.hip); frames are compressed into
   // padded per-frame scratch in batches, packed with the scatter kernel,
   // and the seek table is appended from the host.
-  // Grow-only device scratch shared by the zstd entry points (guarded by
-  // zstd_mu_): per-call hipMalloc/hipFree of GiB-scale scratch dominated
-  // concurrent decompress (config-5 profile) before this.
-  void* zstd_scratch(size_t idx, size_t need) {
-    if (zs_size_[idx] < need) {
-      if (zs_ptr_[idx]) HIP_CHECK(hipFree(zs_ptr_[idx]));
-      zs_ptr_[idx] = nullptr;
-      zs_size_[idx] = 0;
-      HIP_CHECK(hipMalloc(&zs_ptr_[idx], need));
-      zs_size_[idx] = need;
-    }
-    return zs_ptr_[idx];
-  }
-
-  void* dedup_scratch(size_t idx, size_t need) {
-    if (ds_size_[idx] < need) {
-      if (ds_ptr_[idx]) HIP_CHECK(hipFree(ds_ptr_[idx]));
-      ds_ptr_[idx] = nullptr;
-      ds_size_[idx] = 0;
-      HIP_CHECK(hipMalloc(&ds_ptr_[idx], need));
-      ds_size_[idx] = need;
-    }
-    return ds_ptr_[idx];
-  }
-
   uint64_t zstd_compress_device(uintptr_t src_ptr, uint64_t size, uint32_t frame_raw,
                                 uintptr_t dst_ptr, uint64_t dst_cap) {
     HIP_CHECK(hipSetDevice(device_));
@@ -823,12 +696,12 @@ class GpuEngine {
     std::vector<zstdhost::SeekEntry> entries(nframes);
     py::gil_scoped_release release;
     std::lock_guard<std::mutex> zlk(zstd_mu_);
-    void* dscratch = zstd_scratch(0, batch * stride);
-    void* dseqs = zstd_scratch(1, batch * (uint64_t)max_seqs * 12);
-    int64_t* dsizes = reinterpret_cast<int64_t*>(zstd_scratch(2, batch * sizeof(int64_t)));
-    void* dsegs = zstd_scratch(3, batch * sizeof(CopySegHost));
+    void* dscratch = zs_compress_.reserve(batch * stride);
+    void* dseqs = zs_seqs_.reserve(batch * (uint64_t)max_seqs * 12);
+    int64_t* dsizes = zs_sizes_.reserve<int64_t>(batch * sizeof(int64_t));
+    CopySeg* dsegs = zs_segs_.reserve<CopySeg>(batch * sizeof(CopySeg));
     std::vector<int64_t> hsizes(batch);
-    std::vector<CopySegHost> hsegs(batch);
+    std::vector<CopySeg> hsegs(batch);
     uint64_t out = 0;
     for (uint64_t first = 0; first < nframes; first += batch) {
       uint32_t n = (uint32_t)std::min<uint64_t>(batch, nframes - first);
@@ -851,7 +724,7 @@ class GpuEngine {
         out += (uint64_t)hsizes[i];
         if (out > dst_cap) throw std::runtime_error("zstd compress: dst overflow");
       }
-      HIP_CHECK(hipMemcpyAsync(dsegs, hsegs.data(), n * sizeof(CopySegHost),
+      HIP_CHECK(hipMemcpyAsync(dsegs, hsegs.data(), n * sizeof(CopySeg),
                                hipMemcpyHostToDevice, hash_stream_));
       HIP_CHECK(modelx_tar_scatter(dscratch, dsegs, n, hash_stream_));
       HIP_CHECK(hipStreamSynchronize(hash_stream_));
@@ -874,61 +747,32 @@ class GpuEngine {
     HIP_CHECK(hipSetDevice(device_));
     using namespace modelx::zstd;
     py::gil_scoped_release release;
-    // read the seek-table footer
-    if (src_len < 17) throw std::runtime_error("zstd blob too small");
-    uint8_t foot[17];
-    HIP_CHECK(hipMemcpy(foot, reinterpret_cast<char*>(src_ptr) + src_len - 17, 17,
+    const char* src = reinterpret_cast<const char*>(src_ptr);
+    // footer, then the table it describes; the format and every check that
+    // keeps a corrupt blob's offsets from the kernel: zstdhost::parse_seek_*
+    uint8_t foot[zstdhost::kSeekFooterBytes] = {};
+    if (src_len >= sizeof foot)  // a shorter blob is rejected by the parser
+      HIP_CHECK(hipMemcpy(foot, src + src_len - sizeof foot, sizeof foot, hipMemcpyDeviceToHost));
+    zstdhost::SeekFooter ft = zstdhost::parse_seek_footer(foot, src_len);
+    std::vector<uint8_t> traw(ft.table_bytes);
+    HIP_CHECK(hipMemcpy(traw.data(), src + src_len - ft.table_bytes, ft.table_bytes,
                         hipMemcpyDeviceToHost));
-    uint32_t magic = (uint32_t)foot[13] | ((uint32_t)foot[14] << 8) | ((uint32_t)foot[15] << 16) |
-                     ((uint32_t)foot[16] << 24);
-    if (magic != kSeekTableMagic)
-      throw std::runtime_error("zstd blob has no seek table (footer magic mismatch)");
-    bool checksums = foot[12] & 0x80;
-    uint32_t nframes = (uint32_t)foot[8] | ((uint32_t)foot[9] << 8) | ((uint32_t)foot[10] << 16) |
-                       ((uint32_t)foot[11] << 24);
-    uint64_t entry_sz = checksums ? 12 : 8;
-    uint64_t tbl = 8 + (uint64_t)nframes * entry_sz + 9;
-    if (tbl > src_len) throw std::runtime_error("zstd seek table larger than blob");
-    std::vector<uint8_t> traw(tbl);
-    HIP_CHECK(hipMemcpy(traw.data(), reinterpret_cast<char*>(src_ptr) + src_len - tbl, tbl,
-                        hipMemcpyDeviceToHost));
-    // validate the skippable-frame envelope like the CPU parser
-    // (zstd_cpu.cpp parse_seek_table): a corrupt-but-stored blob must throw
-    // here, never hand out-of-bounds frame offsets to the decode kernel
-    auto rd32 = [](const uint8_t* p) {
-      return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) |
-             ((uint32_t)p[3] << 24);
-    };
-    if (rd32(traw.data()) != kMagicSkippableSeek || rd32(traw.data() + 4) != tbl - 8)
-      throw std::runtime_error("zstd seek table: skippable-frame envelope mismatch");
-    std::vector<MxzFrameHost> frames(nframes);
-    uint64_t c_off = 0, d_off = 0;
-    for (uint32_t i = 0; i < nframes; i++) {
-      const uint8_t* e = traw.data() + 8 + (uint64_t)i * entry_sz;
-      uint32_t cs = rd32(e);
-      uint32_t ds = rd32(e + 4);
-      frames[i] = {c_off, cs, d_off, ds};
-      c_off += cs;
-      d_off += ds;
-    }
-    if (c_off != src_len - tbl)
-      throw std::runtime_error("zstd seek table does not cover the frames (" +
-                               std::to_string(c_off) + " != " + std::to_string(src_len - tbl) +
-                               ")");
-    if (d_off > dst_cap) throw std::runtime_error("zstd decompress: dst too small");
+    std::vector<SeekEntry> frames;
+    uint64_t d_total = zstdhost::parse_seek_entries(traw.data(), ft, src_len, &frames);
+    if (d_total > dst_cap) throw std::runtime_error("zstd decompress: dst too small");
+    uint64_t nframes = frames.size();
     uint64_t batch = std::min<uint64_t>(nframes ? nframes : 1, 8192);
     std::lock_guard<std::mutex> zlk(zstd_mu_);
-    void* dframes = zstd_scratch(4, batch * sizeof(MxzFrameHost));
-    void* dlit = zstd_scratch(5, batch * (uint64_t)kBlockMax);
-    int64_t* drc = reinterpret_cast<int64_t*>(zstd_scratch(6, batch * sizeof(int64_t)));
+    SeekEntry* dframes = zs_frames_.reserve<SeekEntry>(batch * sizeof(SeekEntry));
+    void* dlit = zs_lit_.reserve(batch * (uint64_t)kBlockMax);
+    int64_t* drc = zs_rc_.reserve<int64_t>(batch * sizeof(int64_t));
     std::vector<int64_t> hrc(batch);
     for (uint64_t first = 0; first < nframes; first += batch) {
       uint32_t n = (uint32_t)std::min<uint64_t>(batch, nframes - first);
-      HIP_CHECK(hipMemcpyAsync(dframes, frames.data() + first, n * sizeof(MxzFrameHost),
+      HIP_CHECK(hipMemcpyAsync(dframes, frames.data() + first, n * sizeof(SeekEntry),
                                hipMemcpyHostToDevice, hash_stream_));
-      HIP_CHECK(modelx_zstd_decompress_frames(reinterpret_cast<void*>(src_ptr), dframes, n,
-                                              reinterpret_cast<void*>(dst_ptr), dlit, drc,
-                                              zstd_flags(), hash_stream_));
+      HIP_CHECK(modelx_zstd_decompress_frames(src, dframes, n, reinterpret_cast<void*>(dst_ptr),
+                                              dlit, drc, zstd_flags(), hash_stream_));
       HIP_CHECK(hipStreamSynchronize(hash_stream_));
       HIP_CHECK(hipMemcpy(hrc.data(), drc, n * sizeof(int64_t), hipMemcpyDeviceToHost));
       for (uint32_t i = 0; i < n; i++)
@@ -936,7 +780,7 @@ class GpuEngine {
           throw std::runtime_error("zstd decompress kernel failed: frame " +
                                    std::to_string(first + i) + " rc=" + std::to_string(hrc[i]));
     }
-    return d_off;
+    return d_total;
   }
 
   // Batched decode of MANY seekable blobs in one call. The single-blob
@@ -951,110 +795,74 @@ class GpuEngine {
       const std::vector<std::tuple<uintptr_t, uint64_t, uintptr_t, uint64_t>>& items) {
     HIP_CHECK(hipSetDevice(device_));
     using namespace modelx::zstd;
+    constexpr size_t kFoot = zstdhost::kSeekFooterBytes;
     size_t n = items.size();
     std::vector<uint64_t> out(n, 0);
     if (!n) return out;
+    auto src_of = [&](size_t i) { return reinterpret_cast<const char*>(std::get<0>(items[i])); };
+    auto len_of = [&](size_t i) { return std::get<1>(items[i]); };
     py::gil_scoped_release release;
     std::lock_guard<std::mutex> zlk(zstd_mu_);
-    auto rd32 = [](const uint8_t* p) {
-      return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) |
-             ((uint32_t)p[3] << 24);
-    };
     // phase 1: all footers, one sync
-    std::vector<uint8_t> foots(n * 17);
+    std::vector<uint8_t> foots(n * kFoot, 0);
     for (size_t i = 0; i < n; i++) {
-      auto [src, len, dst, cap] = items[i];
-      (void)dst;
-      (void)cap;
-      if (len < 17) throw std::runtime_error("zstd blob too small");
-      HIP_CHECK(hipMemcpyAsync(foots.data() + i * 17, reinterpret_cast<char*>(src) + len - 17,
-                               17, hipMemcpyDeviceToHost, hash_stream_));
-    }
-    HIP_CHECK(hipStreamSynchronize(hash_stream_));
-    std::vector<uint64_t> tbls(n), tbl_off(n);
-    std::vector<uint32_t> nframes(n);
-    std::vector<uint8_t> entry_sz(n);
-    uint64_t total_tbl = 0;
-    for (size_t i = 0; i < n; i++) {
-      const uint8_t* foot = foots.data() + i * 17;
-      if (rd32(foot + 13) != kSeekTableMagic)
-        throw std::runtime_error("zstd blob has no seek table (footer magic mismatch)");
-      nframes[i] = rd32(foot + 8);
-      entry_sz[i] = (foot[12] & 0x80) ? 12 : 8;
-      tbls[i] = 8 + (uint64_t)nframes[i] * entry_sz[i] + 9;
-      if (tbls[i] > std::get<1>(items[i]))
-        throw std::runtime_error("zstd seek table larger than blob");
-      tbl_off[i] = total_tbl;
-      total_tbl += tbls[i];
-    }
-    // phase 2: all tables, one sync
-    std::vector<uint8_t> traw(total_tbl);
-    for (size_t i = 0; i < n; i++) {
-      auto [src, len, dst, cap] = items[i];
-      (void)dst;
-      (void)cap;
-      HIP_CHECK(hipMemcpyAsync(traw.data() + tbl_off[i],
-                               reinterpret_cast<char*>(src) + len - tbls[i], tbls[i],
+      if (len_of(i) < kFoot) continue;  // rejected by the parser below
+      HIP_CHECK(hipMemcpyAsync(foots.data() + i * kFoot, src_of(i) + len_of(i) - kFoot, kFoot,
                                hipMemcpyDeviceToHost, hash_stream_));
     }
     HIP_CHECK(hipStreamSynchronize(hash_stream_));
-    std::vector<MxzFrameHost> frames;
+    std::vector<zstdhost::SeekFooter> foot(n);
+    std::vector<uint64_t> tbl_off(n);
+    uint64_t total_tbl = 0;
+    for (size_t i = 0; i < n; i++) {
+      foot[i] = zstdhost::parse_seek_footer(foots.data() + i * kFoot, len_of(i));
+      tbl_off[i] = total_tbl;
+      total_tbl += foot[i].table_bytes;
+    }
+    // phase 2: all tables, one sync
+    std::vector<uint8_t> traw(total_tbl);
+    for (size_t i = 0; i < n; i++)
+      HIP_CHECK(hipMemcpyAsync(traw.data() + tbl_off[i],
+                               src_of(i) + len_of(i) - foot[i].table_bytes,
+                               foot[i].table_bytes, hipMemcpyDeviceToHost, hash_stream_));
+    HIP_CHECK(hipStreamSynchronize(hash_stream_));
+    std::vector<SeekEntry> frames;
     std::vector<std::pair<size_t, size_t>> item_span(n);  // [first, count) into frames
     uint64_t max_chunk = 1;
     for (size_t i = 0; i < n; i++) {
-      const uint8_t* t = traw.data() + tbl_off[i];
-      if (rd32(t) != kMagicSkippableSeek || rd32(t + 4) != tbls[i] - 8)
-        throw std::runtime_error("zstd seek table: skippable-frame envelope mismatch");
-      uint64_t c_off = 0, d_off = 0;
       size_t first = frames.size();
-      for (uint32_t f = 0; f < nframes[i]; f++) {
-        const uint8_t* e = t + 8 + (uint64_t)f * entry_sz[i];
-        uint32_t cs = rd32(e), ds = rd32(e + 4);
-        frames.push_back({c_off, cs, d_off, ds});
-        c_off += cs;
-        d_off += ds;
-      }
-      if (c_off != std::get<1>(items[i]) - tbls[i])
-        throw std::runtime_error("zstd seek table does not cover the frames");
-      if (d_off > std::get<3>(items[i]))
+      out[i] = zstdhost::parse_seek_entries(traw.data() + tbl_off[i], foot[i], len_of(i),
+                                            &frames);
+      if (out[i] > std::get<3>(items[i]))
         throw std::runtime_error("zstd decompress: dst too small");
       item_span[i] = {first, frames.size() - first};
-      out[i] = d_off;
-      max_chunk = std::max<uint64_t>(max_chunk,
-                                     std::min<uint64_t>(nframes[i] ? nframes[i] : 1, 8192));
+      max_chunk = std::max<uint64_t>(
+          max_chunk, std::min<uint64_t>(foot[i].nframes ? foot[i].nframes : 1, 8192));
     }
     if (frames.empty()) return out;
     // phase 3: one frame-array H2D, decode launches across streams
     size_t ns = streams_.size();
-    void* dframes = zstd_scratch(4, frames.size() * sizeof(MxzFrameHost));
-    int64_t* drc = reinterpret_cast<int64_t*>(
-        zstd_scratch(7, frames.size() * sizeof(int64_t)));
-    void* dlit = zstd_scratch(5, ns * max_chunk * (uint64_t)kBlockMax);
-    HIP_CHECK(hipMemcpyAsync(dframes, frames.data(), frames.size() * sizeof(MxzFrameHost),
+    SeekEntry* dframes = zs_frames_.reserve<SeekEntry>(frames.size() * sizeof(SeekEntry));
+    int64_t* drc = zs_rc_.reserve<int64_t>(frames.size() * sizeof(int64_t));
+    char* dlit = zs_lit_.reserve<char>(ns * max_chunk * (uint64_t)kBlockMax);
+    HIP_CHECK(hipMemcpyAsync(dframes, frames.data(), frames.size() * sizeof(SeekEntry),
                              hipMemcpyHostToDevice, hash_stream_));
-    hipEvent_t staged;
-    HIP_CHECK(hipEventCreateWithFlags(&staged, hipEventDisableTiming));
-    HIP_CHECK(hipEventRecord(staged, hash_stream_));
-    for (size_t s = 0; s < ns; s++) HIP_CHECK(hipStreamWaitEvent(streams_[s], staged, 0));
+    HIP_CHECK(hipEventRecord(zs_staged_, hash_stream_));
+    for (size_t s = 0; s < ns; s++) HIP_CHECK(hipStreamWaitEvent(streams_[s], zs_staged_, 0));
     size_t rr = 0;
     for (size_t i = 0; i < n; i++) {
-      auto [src, len, dst, cap] = items[i];
-      (void)len;
-      (void)cap;
       auto [first, count] = item_span[i];
       for (size_t off = 0; off < count; off += max_chunk) {
         uint32_t nb = (uint32_t)std::min<uint64_t>(max_chunk, count - off);
         size_t sidx = rr++ % ns;
         HIP_CHECK(modelx_zstd_decompress_frames(
-            reinterpret_cast<void*>(src),
-            static_cast<MxzFrameHost*>(dframes) + first + off, nb,
-            reinterpret_cast<void*>(dst),
-            static_cast<char*>(dlit) + sidx * max_chunk * (uint64_t)kBlockMax,
-            drc + first + off, zstd_flags(), streams_[sidx]));
+            src_of(i), dframes + first + off, nb,
+            reinterpret_cast<void*>(std::get<2>(items[i])),
+            dlit + sidx * max_chunk * (uint64_t)kBlockMax, drc + first + off, zstd_flags(),
+            streams_[sidx]));
       }
     }
     for (auto& st : streams_) HIP_CHECK(hipStreamSynchronize(st));
-    hipEventDestroy(staged);
     std::vector<int64_t> hrc(frames.size());
     HIP_CHECK(hipMemcpy(hrc.data(), drc, frames.size() * sizeof(int64_t),
                         hipMemcpyDeviceToHost));
@@ -1089,18 +897,18 @@ class GpuEngine {
     {
       py::gil_scoped_release release;
       std::lock_guard<std::mutex> zlk(zstd_mu_);
-      void* dleaves = zstd_scratch(8, total * 32);
+      char* dleaves = zs_leaves_.reserve<char>(total * 32);
       // ONE launch over all buffers: per-blob launches leave the chip
       // near-idle on small blobs (a 64 MiB blob is only 512 chains)
-      std::vector<ChunkLeavesDescHost> descs(n);
+      std::vector<ChunkLeavesDesc> descs(n);
       for (size_t i = 0; i < n; i++) {
         auto [ptr, size, cs] = items[i];
-        descs[i] = {reinterpret_cast<const void*>(ptr),
-                    static_cast<char*>(dleaves) + off[i] * 32, size, cs,
+        descs[i] = {reinterpret_cast<const uint8_t*>(ptr),
+                    reinterpret_cast<uint8_t*>(dleaves + off[i] * 32), size, cs,
                     (uint32_t)off[i], 0};
       }
-      void* ddescs = zstd_scratch(9, n * sizeof(ChunkLeavesDescHost));
-      HIP_CHECK(hipMemcpyAsync(ddescs, descs.data(), n * sizeof(ChunkLeavesDescHost),
+      ChunkLeavesDesc* ddescs = zs_descs_.reserve<ChunkLeavesDesc>(n * sizeof(ChunkLeavesDesc));
+      HIP_CHECK(hipMemcpyAsync(ddescs, descs.data(), n * sizeof(ChunkLeavesDesc),
                                hipMemcpyHostToDevice, hash_stream_));
       HIP_CHECK(modelx_sha256_chunk_leaves_many(ddescs, (uint32_t)n, (uint32_t)total,
                                                 hash_stream_));
@@ -1133,15 +941,14 @@ class GpuEngine {
     std::lock_guard<std::mutex> lk(dedup_mu_);
     if (cap_pow2 == 0) cap_pow2 = dedup_cap_ ? dedup_cap_ : (1ull << 22);
     if (dedup_cap_ != cap_pow2) {
-      if (dedup_table_) HIP_CHECK(hipFree(dedup_table_));
-      dedup_table_ = nullptr;
-      HIP_CHECK(hipMalloc(&dedup_table_, cap_pow2 * 48));
+      dedup_cap_ = 0;
+      dedup_table_ = DeviceBuffer();  // free first: old and new never coexist
+      dedup_table_ = DeviceBuffer(cap_pow2 * 48);
       dedup_cap_ = cap_pow2;
     }
-    if (!dedup_dropped_)
-      HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&dedup_dropped_), sizeof(uint32_t)));
-    HIP_CHECK(hipMemsetAsync(dedup_table_, 0, dedup_cap_ * 48, hash_stream_));
-    HIP_CHECK(hipMemsetAsync(dedup_dropped_, 0, sizeof(uint32_t), hash_stream_));
+    if (!dedup_dropped_) dedup_dropped_ = DeviceBuffer(sizeof(uint32_t));
+    HIP_CHECK(hipMemsetAsync(dedup_table_.get(), 0, dedup_cap_ * 48, hash_stream_));
+    HIP_CHECK(hipMemsetAsync(dedup_dropped_.get(), 0, sizeof(uint32_t), hash_stream_));
     HIP_CHECK(hipStreamSynchronize(hash_stream_));
   }
 
@@ -1156,21 +963,21 @@ class GpuEngine {
     if (!dedup_table_) {
       // lazy init at default capacity
       uint64_t cap = 1ull << 22;
-      HIP_CHECK(hipMalloc(&dedup_table_, cap * 48));
-      HIP_CHECK(hipMemsetAsync(dedup_table_, 0, cap * 48, hash_stream_));
+      dedup_table_ = DeviceBuffer(cap * 48);
+      HIP_CHECK(hipMemsetAsync(dedup_table_.get(), 0, cap * 48, hash_stream_));
       dedup_cap_ = cap;
-      HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&dedup_dropped_), sizeof(uint32_t)));
-      HIP_CHECK(hipMemsetAsync(dedup_dropped_, 0, sizeof(uint32_t), hash_stream_));
+      dedup_dropped_ = DeviceBuffer(sizeof(uint32_t));
+      HIP_CHECK(hipMemsetAsync(dedup_dropped_.get(), 0, sizeof(uint32_t), hash_stream_));
     }
     uint32_t n = static_cast<uint32_t>(lv.size() / 32);
-    void* dleaves = dedup_scratch(0, lv.size() ? lv.size() : 32);
+    void* dleaves = ds_leaves_.reserve(lv.size() ? lv.size() : 32);
     HIP_CHECK(hipMemcpyAsync(dleaves, lv.data(), lv.size(), hipMemcpyHostToDevice,
                              hash_stream_));
-    HIP_CHECK(modelx_dedup_insert(dleaves, n, base, chunk_size, total, dedup_table_,
-                                  dedup_cap_, dedup_dropped_, hash_stream_));
+    HIP_CHECK(modelx_dedup_insert(dleaves, n, base, chunk_size, total, dedup_table_.get(),
+                                  dedup_cap_, dedup_dropped_.get<uint32_t>(), hash_stream_));
     uint32_t dropped = 0;
     HIP_CHECK(hipStreamSynchronize(hash_stream_));
-    HIP_CHECK(hipMemcpy(&dropped, dedup_dropped_, sizeof dropped, hipMemcpyDeviceToHost));
+    HIP_CHECK(hipMemcpy(&dropped, dedup_dropped_.get(), sizeof dropped, hipMemcpyDeviceToHost));
     return dropped;
   }
 
@@ -1186,13 +993,13 @@ class GpuEngine {
       HIP_CHECK(hipSetDevice(device_));
       py::gil_scoped_release release;
       std::lock_guard<std::mutex> lk(dedup_mu_);
-      void* dleaves = dedup_scratch(0, lv.size());
-      uint64_t* daddr = reinterpret_cast<uint64_t*>(dedup_scratch(1, (uint64_t)n * 8));
-      uint64_t* dlen = reinterpret_cast<uint64_t*>(dedup_scratch(2, (uint64_t)n * 8));
+      void* dleaves = ds_leaves_.reserve(lv.size());
+      uint64_t* daddr = ds_addr_.reserve<uint64_t>((uint64_t)n * 8);
+      uint64_t* dlen = ds_len_.reserve<uint64_t>((uint64_t)n * 8);
       HIP_CHECK(hipMemcpyAsync(dleaves, lv.data(), lv.size(), hipMemcpyHostToDevice,
                                hash_stream_));
-      HIP_CHECK(modelx_dedup_probe(dleaves, n, chunk_size, total, dedup_table_, dedup_cap_,
-                                   daddr, dlen, hash_stream_));
+      HIP_CHECK(modelx_dedup_probe(dleaves, n, chunk_size, total, dedup_table_.get(),
+                                   dedup_cap_, daddr, dlen, hash_stream_));
       HIP_CHECK(modelx_dedup_gather(daddr, dlen, n, dst_ptr, chunk_size, hash_stream_));
       std::vector<uint64_t> haddr(n);
       HIP_CHECK(hipStreamSynchronize(hash_stream_));
@@ -1239,6 +1046,83 @@ class GpuEngine {
     cv_free_.notify_all();
   }
 
+  // The two pinned slots of a double-buffered D2H drain. Both are taken in
+  // ONE wait: sequential acquire_slot() would hold-and-wait and can deadlock
+  // when >= num_slots drains run concurrently. The destructor waits out any
+  // copy still in flight into a slot before the pool can hand it out again.
+  class SlotLease {
+   public:
+    explicit SlotLease(GpuEngine& eng) : eng_(eng) {
+      std::unique_lock<std::mutex> lk(eng_.mu_);
+      eng_.cv_free_.wait(lk, [&] { return eng_.free_.size() >= 2; });
+      for (Slot*& s : slot_) {
+        s = eng_.free_.front();
+        eng_.free_.pop();
+      }
+    }
+    SlotLease(const SlotLease&) = delete;
+    ~SlotLease() {
+      for (int i = 0; i < 2; i++)
+        if (in_flight_[i]) (void)hipEventSynchronize(slot_[i]->event);
+      {
+        std::lock_guard<std::mutex> lk(eng_.mu_);
+        for (Slot* s : slot_) eng_.free_.push(s);
+      }
+      eng_.cv_free_.notify_all();
+    }
+    const char* host(int i) const { return slot_[i]->host; }
+    // async D2H into slot i on st, then record the slot's event
+    hipError_t fill(int i, const char* src, uint64_t len, hipStream_t st) {
+      hipError_t e = hipMemcpyAsync(slot_[i]->host, src, len, hipMemcpyDeviceToHost, st);
+      if (e == hipSuccess) e = hipEventRecord(slot_[i]->event, st);
+      if (e == hipSuccess) in_flight_[i] = true;
+      return e;
+    }
+    hipError_t wait(int i) {
+      in_flight_[i] = false;
+      return hipEventSynchronize(slot_[i]->event);
+    }
+
+   private:
+    GpuEngine& eng_;
+    Slot* slot_[2];
+    bool in_flight_[2] = {false, false};
+  };
+
+  // Stream [src_ptr, src_ptr+size) D2H through two leased pinned slots and
+  // hand each filled (host_ptr, len) to `consume` in order, the copy into
+  // one slot overlapping the consumer's work on the other. `consume`
+  // returning false stops the drain; a HIP error stops it and is returned.
+  template <class Consume>
+  hipError_t drain_device(uintptr_t src_ptr, uint64_t size, Consume&& consume) {
+    if (!size) return hipSuccess;
+    const char* src = reinterpret_cast<const char*>(src_ptr);
+    // streams chosen round-robin so concurrent drains (part uploads, blob
+    // digests) don't serialize on one stream
+    hipStream_t st_a = streams_[push_rr_.fetch_add(1) % streams_.size()];
+    hipStream_t st_b = streams_[push_rr_.fetch_add(1) % streams_.size()];
+    SlotLease lease(*this);
+    int cur = 0, nxt = 1;
+    uint64_t off = 0;
+    uint64_t cur_len = std::min<uint64_t>(slot_bytes_, size);
+    hipError_t e = lease.fill(cur, src, cur_len, st_a);
+    while (e == hipSuccess && off < size) {
+      uint64_t next_off = off + cur_len;
+      uint64_t next_len = next_off < size ? std::min<uint64_t>(slot_bytes_, size - next_off) : 0;
+      if (next_len) {
+        e = lease.fill(nxt, src + next_off, next_len, st_b);
+        if (e != hipSuccess) break;
+        std::swap(st_a, st_b);
+      }
+      e = lease.wait(cur);
+      if (e != hipSuccess || !consume(lease.host(cur), cur_len)) break;
+      std::swap(cur, nxt);
+      off = next_off;
+      cur_len = next_len;
+    }
+    return e;
+  }
+
   // start a ranged GET and validate the response head; body is then read
   // with read_body_exact by the caller. STRICT framing: must answer 206
   // with Content-Length == the requested span — a 200 (full object) or a
@@ -1270,16 +1154,21 @@ class GpuEngine {
   hipStream_t hash_stream_ = nullptr;
   std::mutex mu_;
   std::condition_variable cv_free_, cv_pending_;
-  std::mutex zstd_mu_;
-  void* zs_ptr_[10] = {};
-  size_t zs_size_[10] = {};
   ConnPool conn_pool_;
+  // Everything below zstd_mu_ up to dedup_mu_ is guarded by zstd_mu_;
+  // everything below dedup_mu_ by dedup_mu_. A scratch buffer is only valid
+  // while its mutex is held: the next holder may reallocate it.
+  std::mutex zstd_mu_;
+  DeviceScratch zs_compress_, zs_seqs_, zs_sizes_, zs_segs_;  // zstd_compress_device
+  // decode, single-blob and batched alike (rc: one entry per launched frame)
+  DeviceScratch zs_frames_, zs_lit_, zs_rc_;
+  hipEvent_t zs_staged_ = nullptr;  // frame array staged -> decode streams may start
+  DeviceScratch zs_leaves_, zs_descs_;  // sha256_chunk_leaves_many
   std::mutex dedup_mu_;
-  void* dedup_table_ = nullptr;
+  DeviceBuffer dedup_table_;
   uint64_t dedup_cap_ = 0;
-  uint32_t* dedup_dropped_ = nullptr;
-  void* ds_ptr_[3] = {};  // dedup scratch: leaves, addr, len (under dedup_mu_)
-  size_t ds_size_[3] = {};
+  DeviceBuffer dedup_dropped_;  // one uint32_t
+  DeviceScratch ds_leaves_, ds_addr_, ds_len_;
 };
 
 bool hip_available() {
@@ -1407,13 +1296,28 @@ PYBIND11_MODULE(_core, m) {
     std::string s = data;
     return zstdhost::content_size(reinterpret_cast<const uint8_t*>(s.data()), s.size());
   });
-  m.def("zstd_frames", [](py::bytes data) {
+  auto entry_tuples = [](const std::vector<SeekEntry>& t) {
+    py::list out;
+    for (auto& e : t) out.append(py::make_tuple(e.c_off, e.c_size, e.d_off, e.d_size));
+    return out;
+  };
+  m.def("zstd_frames", [=](py::bytes data) {
     std::string s = data;
     auto t = zstdhost::parse_seek_table(reinterpret_cast<const uint8_t*>(s.data()), s.size());
     if (t.empty())
       t = zstdhost::walk_frames(reinterpret_cast<const uint8_t*>(s.data()), s.size());
-    py::list out;
-    for (auto& e : t) out.append(py::make_tuple(e.c_off, e.c_size, e.d_off, e.d_size));
-    return out;
+    return entry_tuples(t);
+  });
+  // The strict two-step seek-table parser the device decode paths rely on:
+  // raises instead of falling back, so the GPU-less suite can test it.
+  m.def("zstd_seek_table", [=](py::bytes data) {
+    std::string s = data;
+    const uint8_t* blob = reinterpret_cast<const uint8_t*>(s.data());
+    uint8_t foot[zstdhost::kSeekFooterBytes] = {};
+    if (s.size() >= sizeof foot) memcpy(foot, blob + s.size() - sizeof foot, sizeof foot);
+    zstdhost::SeekFooter ft = zstdhost::parse_seek_footer(foot, s.size());
+    std::vector<SeekEntry> t;
+    zstdhost::parse_seek_entries(blob + s.size() - ft.table_bytes, ft, s.size(), &t);
+    return entry_tuples(t);
   });
 }

@@ -24,32 +24,56 @@ using namespace modelx::zstd;
 static const u32 kSkippableMagicMin = 0x184D2A50u;
 static const u32 kSkippableMagicMax = 0x184D2A5Fu;
 
-std::vector<SeekEntry> parse_seek_table(const uint8_t* blob, size_t len) {
-  std::vector<SeekEntry> out;
-  if (len < 17) return out;
-  // footer: u32 num_frames, u8 descriptor, u32 seekable magic
-  if (mx_read_le32(blob + len - 4) != kSeekTableMagic) return out;
-  uint8_t desc = blob[len - 5];
-  bool checksums = desc & 0x80;
-  uint32_t nframes = mx_read_le32(blob + len - 9);
-  size_t entry_sz = checksums ? 12 : 8;
-  uint64_t tbl_payload = (uint64_t)nframes * entry_sz + 9;
-  if (tbl_payload + 8 > len) return out;
-  const uint8_t* skf = blob + len - tbl_payload - 8;
-  if (mx_read_le32(skf) != kMagicSkippableSeek) return out;
-  if (mx_read_le32(skf + 4) != tbl_payload) return out;
-  const uint8_t* e = skf + 8;
+SeekFooter parse_seek_footer(const uint8_t* tail17, uint64_t blob_len) {
+  if (blob_len < kSeekFooterBytes) throw std::runtime_error("zstd blob too small");
+  // footer = the tail's last 9 bytes: u32 num_frames, u8 descriptor, u32
+  // seekable magic
+  const uint8_t* foot = tail17 + kSeekFooterBytes - 9;
+  if (mx_read_le32(foot + 5) != kSeekTableMagic)
+    throw std::runtime_error("zstd blob has no seek table (footer magic mismatch)");
+  SeekFooter f;
+  f.nframes = mx_read_le32(foot);
+  f.entry_bytes = (foot[4] & 0x80) ? 12 : 8;  // descriptor bit 7: per-frame checksums
+  f.table_bytes = 8 + (uint64_t)f.nframes * f.entry_bytes + 9;
+  if (f.table_bytes > blob_len) throw std::runtime_error("zstd seek table larger than blob");
+  return f;
+}
+
+uint64_t parse_seek_entries(const uint8_t* table, const SeekFooter& f, uint64_t blob_len,
+                            std::vector<SeekEntry>* out) {
+  // validate the skippable-frame envelope: a corrupt-but-stored blob must
+  // throw here, never hand out-of-bounds frame offsets to a decoder
+  if (mx_read_le32(table) != kMagicSkippableSeek || mx_read_le32(table + 4) != f.table_bytes - 8)
+    throw std::runtime_error("zstd seek table: skippable-frame envelope mismatch");
+  size_t first = out->size();
+  out->reserve(first + f.nframes);
+  const uint8_t* e = table + 8;
   uint64_t c_off = 0, d_off = 0;
-  out.reserve(nframes);
-  for (uint32_t i = 0; i < nframes; i++) {
+  for (uint32_t i = 0; i < f.nframes; i++, e += f.entry_bytes) {
     uint32_t cs = mx_read_le32(e);
     uint32_t ds = mx_read_le32(e + 4);
-    out.push_back({c_off, cs, d_off, ds});
+    out->push_back({c_off, cs, d_off, ds});
     c_off += cs;
     d_off += ds;
-    e += entry_sz;
   }
-  if (c_off != (uint64_t)(skf - blob)) return {};  // table doesn't cover the frames
+  if (c_off != blob_len - f.table_bytes) {
+    out->resize(first);
+    throw std::runtime_error("zstd seek table does not cover the frames (" +
+                             std::to_string(c_off) + " != " +
+                             std::to_string(blob_len - f.table_bytes) + ")");
+  }
+  return d_off;
+}
+
+std::vector<SeekEntry> parse_seek_table(const uint8_t* blob, size_t len) {
+  std::vector<SeekEntry> out;
+  try {
+    if (len < kSeekFooterBytes) return out;
+    SeekFooter f = parse_seek_footer(blob + len - kSeekFooterBytes, len);
+    parse_seek_entries(blob + len - f.table_bytes, f, len, &out);
+  } catch (const std::runtime_error&) {
+    out.clear();  // no usable table: the caller falls back to walk_frames
+  }
   return out;
 }
 

@@ -239,6 +239,37 @@ class TestZstdKernels:
         assert m == len(data)
         assert torch.equal(back, src)
 
+    def test_corrupt_seek_table_rejected_on_host(self, engine):
+        """A damaged blob tail is refused by the host-side seek-table
+        validation of both device entry points — before any decode kernel
+        is launched — and the engine's scratch and locks survive the
+        throws: the same engine still decodes the good blob."""
+        import util_seek
+
+        data, blob = util_seek.three_frame_blob()
+        good = torch.frombuffer(bytearray(blob), dtype=torch.uint8).cuda()
+        dst = [torch.empty(len(data), dtype=torch.uint8, device="cuda") for _ in range(3)]
+        for name, bad_bytes in util_seek.corruptions(blob).items():
+            bad = torch.frombuffer(bytearray(bad_bytes), dtype=torch.uint8).cuda()
+            with pytest.raises(RuntimeError):
+                engine.zstd_decompress_device(bad.data_ptr(), len(bad_bytes),
+                                              dst[0].data_ptr(), len(data))
+            with pytest.raises(RuntimeError):
+                engine.zstd_decompress_many(
+                    [(good.data_ptr(), len(blob), dst[0].data_ptr(), len(data)),
+                     (bad.data_ptr(), len(bad_bytes), dst[1].data_ptr(), len(data)),
+                     (good.data_ptr(), len(blob), dst[2].data_ptr(), len(data))])
+        for d in dst:
+            d.zero_()
+        torch.cuda.synchronize()
+        n = engine.zstd_decompress_device(good.data_ptr(), len(blob),
+                                          dst[0].data_ptr(), len(data))
+        sizes = engine.zstd_decompress_many(
+            [(good.data_ptr(), len(blob), d.data_ptr(), len(data)) for d in dst[1:]])
+        assert n == len(data) and sizes == [len(data)] * 2
+        for d in dst:
+            assert bytes(d.cpu().numpy().tobytes()) == data
+
 
 class TestZstdGpuClient:
     def test_push_pull_compressed(self, tmp_path):
@@ -473,6 +504,60 @@ class TestPushFaultInjection:
             assert torch.equal(back["w.bin"], src)
         finally:
             mdx.stop()
+            s3d.stop()
+
+    def test_drain_boundaries_on_minimum_pool(self, tmp_path):
+        """Multi-slot parts plus a part ending a few bytes past a slot edge,
+        pushed through the smallest pool a drain can run on (2 slots): the
+        prefetch / swap / tail steps of the double-buffered D2H drain."""
+        from util_servers import start_modelxd_s3, start_s3d
+
+        from modelx_amd.client.gpu import GpuClient
+
+        s3d = start_s3d(str(tmp_path / "s3"))
+        mdx = start_modelxd_s3(s3d.url, redirect=True)
+        try:
+            g = GpuClient(mdx.url, device=0, num_slots=2, slot_bytes=1 << 20)
+            src = torch.randint(0, 256, ((9 << 20) + 5,), dtype=torch.uint8,
+                                device="cuda:0")
+            g.push_from_gpu("gpu/drain", "v1", {"w.bin": src}, part_bytes=4 << 20)
+            back = g.pull_to_gpu("gpu/drain", "v1")
+            assert torch.equal(back["w.bin"], src)
+        finally:
+            mdx.stop()
+            s3d.stop()
+
+    def test_slots_return_after_failed_push(self, tmp_path):
+        """Every failed push_part_from_device gives both pinned slots back:
+        on a 2-slot engine a single lost slot would block the next drain
+        forever (shown here as a failed assertion, not a hang)."""
+        import threading
+
+        from util_servers import BUCKET, start_s3d
+
+        from modelx_amd import _core
+
+        s3d = start_s3d(str(tmp_path / "s3"))
+        try:
+            eng = _core.GpuEngine(device=0, num_slots=2, slot_bytes=1 << 20, num_streams=4)
+            size = 3 << 20
+            data = torch.randint(0, 256, (size,), dtype=torch.uint8)
+            dev = data.cuda()
+            torch.cuda.synchronize()
+            for _ in range(3):
+                # unsigned PUT: s3d answers 403
+                with pytest.raises(RuntimeError):
+                    eng.push_part_from_device(f"{s3d.url}/{BUCKET}/unsigned", "PUT", {},
+                                              dev.data_ptr(), size)
+            got = []
+            t = threading.Thread(
+                target=lambda: got.append(eng.sha256_canonical_device(dev.data_ptr(), size)),
+                daemon=True)
+            t.start()
+            t.join(20)
+            assert not t.is_alive(), "canonical digest blocked: a pinned slot was lost"
+            assert got == [hashlib.sha256(data.numpy().tobytes()).digest()]
+        finally:
             s3d.stop()
 
 

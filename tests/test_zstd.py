@@ -23,6 +23,7 @@ from modelx_amd.client import Client
 from modelx_amd.config import ModelConfig
 from modelx_amd.wire import types
 
+import util_seek
 from util_servers import start_modelxd_local
 
 
@@ -141,6 +142,56 @@ class TestCpuCodec:
         blob = _core.zstd_compress_cpu(data, 128 << 10)
         with pytest.raises(RuntimeError):
             _core.zstd_decompress_cpu(blob[: len(blob) // 2])
+
+
+_CORRUPTIONS = ["truncated-16", "footer-magic", "nframes-exceeds-blob", "envelope-magic",
+                "envelope-length", "entry-csize"]
+
+
+class TestStrictSeekTable:
+    """_core.zstd_seek_table is the strict two-step parser the device decode
+    paths depend on (zstdhost::parse_seek_footer / parse_seek_entries); the
+    lenient zstd_frames wraps the same two steps and falls back to a frame
+    walk."""
+
+    @pytest.mark.parametrize("data", [b"", b"a", util_seek.three_frame_blob()[0]],
+                             ids=["empty", "one-byte", "three-frames"])
+    def test_good_blob_matches_zstd_frames(self, data):
+        blob = _core.zstd_compress_cpu(data, util_seek.FRAME_RAW)
+        table = _core.zstd_seek_table(blob)
+        assert table == _core.zstd_frames(blob)
+        assert len(table) == max(1, -(-len(data) // util_seek.FRAME_RAW))
+        assert sum(e[3] for e in table) == len(data)
+
+    def test_corruption_set_is_complete(self):
+        _, blob = util_seek.three_frame_blob()
+        assert sorted(util_seek.corruptions(blob)) == sorted(_CORRUPTIONS)
+
+    @pytest.mark.parametrize("name", _CORRUPTIONS)
+    def test_corrupt_tail_raises(self, name):
+        _, blob = util_seek.three_frame_blob()
+        with pytest.raises(RuntimeError):
+            _core.zstd_seek_table(util_seek.corruptions(blob)[name])
+
+    @pytest.mark.parametrize("name", _CORRUPTIONS)
+    def test_lenient_parser_keeps_fallback_contract(self, name):
+        # parse_seek_table still returns empty on a bad table, so the callers
+        # fall back to walk_frames: a list from zstd_frames, and a clean
+        # result or RuntimeError (never a crash) from the decoder
+        _, blob = util_seek.three_frame_blob()
+        bad = util_seek.corruptions(blob)[name]
+        assert isinstance(_core.zstd_frames(bad), list)
+        try:
+            out = _core.zstd_decompress_cpu(bad)
+        except RuntimeError:
+            return
+        assert isinstance(out, bytes)
+
+    def test_checksum_flag_widens_entries(self):
+        _, blob = util_seek.three_frame_blob()
+        wide = util_seek.with_checksum_flag(blob)
+        assert len(wide) == len(blob) + 3 * 4
+        assert _core.zstd_seek_table(wide) == _core.zstd_seek_table(blob)
 
 
 class TestZstdPushPull:
