@@ -30,6 +30,15 @@ struct CopySeg {
   uint64_t len;
 };
 
+// Pack segment: copies len bytes from the absolute device address src_ptr to
+// tar + dst_off, then writes zero_len zero bytes after them.
+struct PackSeg {
+  uint64_t src_ptr;
+  uint64_t dst_off;
+  uint64_t len;
+  uint64_t zero_len;
+};
+
 struct ChunkLeavesDesc {
   const uint8_t* data;
   uint8_t* leaves;
@@ -56,6 +65,8 @@ hipError_t modelx_tar_index(const void* tar, uint64_t tar_len, modelx::abi::TarE
                             hipStream_t stream);
 hipError_t modelx_tar_scatter(const void* tar, const modelx::abi::CopySeg* segs, uint32_t nsegs,
                               hipStream_t stream);
+hipError_t modelx_tar_pack(void* tar, const modelx::abi::PackSeg* segs, uint32_t nsegs,
+                           hipStream_t stream);
 hipError_t modelx_zstd_decompress_frames(const void* src,
                                          const modelx::zstdhost::SeekEntry* frames_dev,
                                          uint32_t nframes, void* dst, void* lit_scratch,

@@ -41,6 +41,7 @@
 
 #include "modelx/device_abi.hpp"
 #include "modelx/http.hpp"
+#include "modelx/tar_host.hpp"
 #include "modelx/zstd_core.hpp"
 #include "modelx/zstd_host.hpp"
 
@@ -48,6 +49,7 @@ namespace py = pybind11;
 using namespace modelx;
 using modelx::abi::ChunkLeavesDesc;
 using modelx::abi::CopySeg;
+using modelx::abi::PackSeg;
 using modelx::abi::TarEntry;
 using zstdhost::SeekEntry;
 
@@ -559,7 +561,7 @@ class GpuEngine {
   // blocks with the scatter kernel, and reads names from one D2H copy.
   py::list tar_index(uintptr_t tar_ptr, uint64_t tar_len) {
     HIP_CHECK(hipSetDevice(device_));
-    uint32_t max_entries = 65536;
+    uint32_t max_entries = tarhost::kMaxIndexEntries;  // tar_pack emits no more
     std::vector<TarEntry> entries;
     uint32_t count = 0, error = 0;
     {
@@ -675,6 +677,56 @@ class GpuEngine {
     HIP_CHECK(modelx_tar_scatter(reinterpret_cast<void*>(tar_ptr), dsegs.get<CopySeg>(),
                                  static_cast<uint32_t>(pieces.size()), hash_stream_));
     HIP_CHECK(hipStreamSynchronize(hash_stream_));
+  }
+
+  // Pack device buffers into one plain-tar archive at dst_ptr (device):
+  // members = [(name, src_dev_ptr, size), ...] in archive order. The layout
+  // and header bytes come from tar_host.hpp; the kernel writes every byte of
+  // [0, total) — headers, payload pieces, 512 B padding and the end marker —
+  // so the destination needs no memset. Returns total.
+  uint64_t tar_pack(uintptr_t dst_ptr, uint64_t dst_cap,
+                    const std::vector<std::tuple<std::string, uintptr_t, uint64_t>>& members) {
+    std::vector<std::pair<std::string, uint64_t>> names;
+    names.reserve(members.size());
+    for (auto& m : members) names.emplace_back(std::get<0>(m), std::get<2>(m));
+    tarhost::PackLayout lay = tarhost::pack_layout(names);
+    if (lay.total > dst_cap)
+      throw std::runtime_error("tar_pack: archive of " + std::to_string(lay.total) +
+                               " bytes exceeds destination capacity " +
+                               std::to_string(dst_cap));
+    if (dst_ptr & 15u) throw std::runtime_error("tar_pack: destination is not 16-byte aligned");
+    HIP_CHECK(hipSetDevice(device_));
+    py::gil_scoped_release release;
+    DeviceBuffer dheaders(std::max<size_t>(lay.headers.size(), 1));
+    uint64_t hbase = reinterpret_cast<uint64_t>(dheaders.get());
+    // header regions, then payloads in <=4 MiB pieces (the last one carries
+    // the zero padding up to the 512 B boundary), then the end marker
+    std::vector<PackSeg> segs;
+    constexpr uint64_t kPiece = 4ull << 20;
+    uint64_t hoff = 0;
+    for (size_t i = 0; i < members.size(); i++) {
+      const tarhost::PackEntry& e = lay.entries[i];
+      segs.push_back({hbase + hoff, e.header_off, e.header_len, 0});
+      hoff += e.header_len;
+      uint64_t src = std::get<1>(members[i]);
+      for (uint64_t off = 0; off < e.size; off += kPiece) {
+        uint64_t len = std::min(kPiece, e.size - off);
+        bool last = off + len == e.size;
+        segs.push_back({src + off, e.payload_off + off, len,
+                        last ? tarhost::pad512(e.size) - e.size : 0});
+      }
+    }
+    segs.push_back({0, lay.total - 2 * tarhost::kBlock, 0, 2 * tarhost::kBlock});
+    DeviceBuffer dsegs(segs.size() * sizeof(PackSeg));
+    if (!lay.headers.empty())
+      HIP_CHECK(hipMemcpyAsync(dheaders.get(), lay.headers.data(), lay.headers.size(),
+                               hipMemcpyHostToDevice, hash_stream_));
+    HIP_CHECK(hipMemcpyAsync(dsegs.get(), segs.data(), segs.size() * sizeof(PackSeg),
+                             hipMemcpyHostToDevice, hash_stream_));
+    HIP_CHECK(modelx_tar_pack(reinterpret_cast<void*>(dst_ptr), dsegs.get<PackSeg>(),
+                              static_cast<uint32_t>(segs.size()), hash_stream_));
+    HIP_CHECK(hipStreamSynchronize(hash_stream_));
+    return lay.total;
   }
 
   // ------------------------------------------------------------- zstd ----
@@ -1219,6 +1271,8 @@ PYBIND11_MODULE(_core, m) {
            py::arg("method"), py::arg("headers"), py::arg("src_ptr"), py::arg("size"))
       .def("tar_index", &GpuEngine::tar_index, py::arg("tar_ptr"), py::arg("tar_len"))
       .def("tar_scatter", &GpuEngine::tar_scatter, py::arg("tar_ptr"), py::arg("segs"))
+      .def("tar_pack", &GpuEngine::tar_pack, py::arg("dst_ptr"), py::arg("dst_cap"),
+           py::arg("members"))
       .def("dedup_reset", &GpuEngine::dedup_reset, py::arg("cap_pow2") = (uint64_t)0)
       .def("dedup_register", &GpuEngine::dedup_register, py::arg("leaves"), py::arg("base"),
            py::arg("chunk_size"), py::arg("total"))
@@ -1233,6 +1287,29 @@ PYBIND11_MODULE(_core, m) {
            py::arg("src_len"), py::arg("dst_ptr"), py::arg("dst_cap"))
       .def("synchronize", &GpuEngine::synchronize);
 
+  // Tar layout for an ordered [(name, size)] member list (tar_host.hpp):
+  // header bytes, per-member offsets and the archive length. No GPU needed;
+  // GpuEngine::tar_pack writes exactly this archive.
+  m.def(
+      "tar_pack_layout",
+      [](const std::vector<std::pair<std::string, uint64_t>>& members) {
+        tarhost::PackLayout lay = tarhost::pack_layout(members);
+        py::list entries;
+        for (auto& e : lay.entries) {
+          py::dict d;
+          d["header_off"] = e.header_off;
+          d["header_len"] = e.header_len;
+          d["payload_off"] = e.payload_off;
+          d["size"] = e.size;
+          entries.append(std::move(d));
+        }
+        py::dict out;
+        out["headers"] = py::bytes(lay.headers);
+        out["entries"] = entries;
+        out["total"] = lay.total;
+        return out;
+      },
+      py::arg("members"));
   m.def("zstd_compress_bound", &GpuEngine::zstd_compress_bound, py::arg("size"),
         py::arg("frame_raw") = (uint32_t)(128 << 10));
   // CPU codec path (same header-only core as the kernels) — used by the

@@ -609,9 +609,13 @@ class GpuClient:
         return outs
 
     def pull_to_gpu(self, repository: str, version: str = "",
-                    verify: bool = True, parallel: int = 1) -> Dict[str, "torch.Tensor"]:
-        """Pull every file blob of a manifest into HBM. Directory (tar.gz)
-        blobs are landed as raw archive bytes under their blob name.
+                    verify: bool = True, parallel: int = 1,
+                    expand_dirs: bool = False) -> Dict[str, "torch.Tensor"]:
+        """Pull every file blob of a manifest into HBM. Directory blobs are
+        landed as raw archive bytes under their blob name; with
+        ``expand_dirs=True`` plain-tar and tar+gz directory blobs go through
+        ``pull_dir_to_gpu`` instead and their members appear under the
+        archive names (``"shards/layer0/w.bin"``), the blob's own name not.
         ``parallel`` > 1 pulls blobs concurrently (reentrant engine; right
         for many-shard manifests where per-blob latency would stack).
         Multiple +zstd blobs decode through the batched engine call."""
@@ -647,14 +651,36 @@ class GpuClient:
             return desc.name, self.pull_blob_to_device(repository, desc, verify=verify,
                                                        plan_entry=entry)
 
-        rest = plain_descs + zstd_descs
-        if parallel > 1 and len(rest) > 1:
+        dir_descs = []
+        if expand_dirs:
+            dir_types = (types.MEDIA_TYPE_MODEL_DIRECTORY_TAR,
+                         types.MEDIA_TYPE_MODEL_DIRECTORY_TARGZ)
+            dir_descs = [d for d in plain_descs if d.media_type in dir_types]
+            plain_descs = [d for d in plain_descs if d.media_type not in dir_types]
+
+        def one_dir(desc):
+            return self.pull_dir_to_gpu(repository, desc, verify=verify,
+                                        plan_entry=plan_blobs.get(desc.digest))
+
+        # file blobs and directory blobs share one pool; each job yields
+        # {name: tensor}
+        jobs = [lambda d=d: dict([one(d)]) for d in plain_descs + zstd_descs]
+        jobs += [lambda d=d: one_dir(d) for d in dir_descs]
+        if parallel > 1 and len(jobs) > 1:
             from concurrent.futures import ThreadPoolExecutor
 
             with ThreadPoolExecutor(max_workers=parallel) as ex:
-                out.update(dict(ex.map(one, rest)))
+                parts = list(ex.map(lambda job: job(), jobs))
         else:
-            out.update(dict(one(d) for d in rest))
+            parts = [job() for job in jobs]
+        for part in parts:
+            if dir_descs:
+                clash = sorted(set(part) & set(out))
+                if clash:
+                    raise er.ModelxError(
+                        er.ErrCode.MANIFEST_INVALID,
+                        f"expand_dirs: {clash[0]!r} is named by more than one blob")
+            out.update(part)
         return out
 
     def pull_many(self, repository: str, versions, parallel: int = 6,
@@ -794,17 +820,22 @@ class GpuClient:
                                 "seconds": time.monotonic() - t0})
         return archive, tar_len
 
-    def pull_dir_to_gpu(self, repository: str, desc: types.Descriptor
+    def pull_dir_to_gpu(self, repository: str, desc: types.Descriptor,
+                        verify: bool = True, plan_entry=None
                         ) -> Dict[str, "torch.Tensor"]:
         """Land a directory blob and scatter its files into per-file HBM
         tensors with the CDNA4 tar kernels (core/hip/tar.hip). Plain-tar
         blobs (MEDIA_TYPE_MODEL_DIRECTORY_TAR) stay on-GPU end to end;
         tar+gz compat blobs are inflated on CPU first (gzip is sequential —
-        the GPU-native path is the plain-tar format)."""
+        the GPU-native path is the plain-tar format). ``verify`` and
+        ``plan_entry`` are those of ``pull_blob_to_device`` and apply to
+        plain-tar blobs; the tar+gz stream always digests the stored bytes
+        as it goes and locates the blob itself."""
         import torch
 
         if desc.media_type == types.MEDIA_TYPE_MODEL_DIRECTORY_TAR:
-            archive = self.pull_blob_to_device(repository, desc)
+            archive = self.pull_blob_to_device(repository, desc, verify=verify,
+                                               plan_entry=plan_entry)
             tar_len = desc.size
         elif desc.media_type == types.MEDIA_TYPE_MODEL_DIRECTORY_TARGZ:
             archive, tar_len = self._stream_targz_to_device(repository, desc)
@@ -823,6 +854,43 @@ class GpuClient:
         if segs:
             self.engine.tar_scatter(archive.data_ptr(), segs)
         return out
+
+    def pack_dir_on_gpu(self, name: str,
+                        files: Dict[str, "torch.Tensor"]) -> "torch.Tensor":
+        """Pack device tensors into one plain-tar archive in HBM (the pack
+        kernel of core/hip/tar.hip) — the push-side inverse of
+        ``pull_dir_to_gpu``. Members are ``f"{name}/{relpath}"`` sorted by
+        name, with deterministic headers, so equal inputs give byte-equal
+        archives. Tensors must live on this client's device and be
+        contiguous (any dtype: the member is the tensor's raw bytes)."""
+        import time
+
+        import torch
+
+        members = []
+        for rel in sorted(files):
+            t = files[rel]
+            if not isinstance(t, torch.Tensor):
+                raise ValueError(f"{name}/{rel}: not a torch.Tensor")
+            if not t.is_cuda or t.device.index != self.device:
+                raise ValueError(f"{name}/{rel}: tensor is on {t.device}, "
+                                 f"not on cuda:{self.device}")
+            if not t.is_contiguous():
+                raise ValueError(f"{name}/{rel}: tensor is not contiguous")
+            members.append((f"{name}/{rel}", t.data_ptr(), t.numel() * t.element_size()))
+        # names and sizes are validated here, before any device work
+        total = _core().tar_pack_layout([(n, s) for n, _, s in members])["total"]
+        self._sync_producers()
+        t0 = time.monotonic()
+        archive = torch.empty(total, dtype=torch.uint8, device=f"cuda:{self.device}")
+        # `files` keeps every source tensor alive: tar_pack returns only
+        # after its stream has synchronized
+        packed = self.engine.tar_pack(archive.data_ptr(), total, members)
+        assert packed == total
+        self.last_stats.append({"phase": "gpu-tar-pack", "bytes": total,
+                                "members": len(members),
+                                "seconds": time.monotonic() - t0})
+        return archive
 
     # -------------------------------------------------------------- push --
 
@@ -949,7 +1017,9 @@ class GpuClient:
                       tensors: Dict[str, "torch.Tensor"], config_yaml: str = "",
                       chunk_size: int = DEFAULT_GPU_CHUNK,
                       part_bytes: int = DEFAULT_PART_BYTES,
-                      compress: str = "", digest_mode: str = "chunked") -> types.Manifest:
+                      compress: str = "", digest_mode: str = "chunked",
+                      dirs: Optional[Dict[str, Dict[str, "torch.Tensor"]]] = None
+                      ) -> types.Manifest:
         """Digest on GPU → presigned multipart upload → manifest PUT last.
         With ``compress="zstd"`` each tensor is compressed on-GPU into a
         seekable multi-frame zstd blob (core/hip/zstd.hip) first; the
@@ -963,7 +1033,17 @@ class GpuClient:
         chunk-digest annotation, exactly like the CPU push path. The
         canonical chain streams D2H through the pinned ring onto the CPU's
         SHA-NI units. Default ``"chunked"`` keeps the all-GPU digest as the
-        main digest (fastest; reference clients lose only verification)."""
+        main digest (fastest; reference clients lose only verification).
+
+        ``dirs`` maps a directory name to ``{relpath: tensor}``: each entry is
+        packed on-GPU into one plain-tar archive (``pack_dir_on_gpu``) and
+        pushed as a single MEDIA_TYPE_MODEL_DIRECTORY_TAR blob with the same
+        digests, annotations and leaves sidecar as a file blob — many small
+        tensors cost one blob's control-plane round trips, not one per
+        tensor. ``pull_dir_to_gpu`` and the CPU ``Client.pull`` both read it
+        back. Every directory is packed (and so validated) before the first
+        upload, so until the push returns HBM holds each directory twice: the
+        source tensors and their archive."""
         import torch
 
         if compress not in ("", "zstd"):
@@ -971,6 +1051,35 @@ class GpuClient:
         if digest_mode not in ("chunked", "sha256"):
             raise er.ModelxError(er.ErrCode.UNSUPPORTED,
                                  f"unknown digest_mode {digest_mode!r}")
+        dir_names = set()
+        if dirs:
+            if compress:
+                raise er.ModelxError(er.ErrCode.UNSUPPORTED,
+                                     "dirs cannot be combined with compress: "
+                                     "there is no tar+zstd directory media type")
+            # every descriptor name the manifest will carry must be unique:
+            # the config, each blob and each blob's leaves sidecar
+            taken = {"modelx.yaml"}
+            for tname in tensors:
+                taken.update((tname, tname + ".leaves"))
+            for dname in dirs:
+                if "/" in dname:
+                    raise ValueError(f"directory name {dname!r} contains '/'")
+                for n in (dname, dname + ".leaves"):
+                    if n in taken:
+                        raise ValueError(f"directory {dname!r}: the name {n!r} is "
+                                         "already used by another blob of this push")
+                taken.update((dname, dname + ".leaves"))
+            # pack (and thereby validate) every directory before the first
+            # upload; the archives then travel as ordinary device blobs
+            tensors = dict(tensors)
+            for dname, files in dirs.items():
+                tensors[dname] = self.pack_dir_on_gpu(dname, files)
+                dir_names.add(dname)
+
+        def blob_media_type(name: str) -> str:
+            return (types.MEDIA_TYPE_MODEL_DIRECTORY_TAR if name in dir_names
+                    else types.MEDIA_TYPE_MODEL_FILE)
         manifest = types.Manifest(media_type=types.MEDIA_TYPE_MODEL_MANIFEST_JSON)
         now = datetime.now(timezone.utc)
         # config blob (small, CPU)
@@ -1026,7 +1135,7 @@ class GpuClient:
                                                     leaves_list, sizes):
                 leaves_digest = dg.sha256_digest(lv)
                 descs.append(types.Descriptor(
-                    name=name, media_type=types.MEDIA_TYPE_MODEL_FILE,
+                    name=name, media_type=blob_media_type(name),
                     digest=main, size=s, modified=now,
                     annotations={types.ANNOTATION_CHUNK_DIGEST: root,
                                  types.ANNOTATION_CHUNK_SIZE: str(chunk_size),
@@ -1058,7 +1167,7 @@ class GpuClient:
             import time
 
             size = t.numel() * t.element_size()
-            media_type = types.MEDIA_TYPE_MODEL_FILE
+            media_type = blob_media_type(name)
             extra_notes: Dict[str, str] = {}
             push_ptr, push_size = t.data_ptr(), size
             comp_keep = None  # keep the compressed tensor alive until pushed
