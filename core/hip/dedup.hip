@@ -5,14 +5,22 @@
 // Replaces (reference): HEAD-based whole-blob dedup only
 // (pkg/client/push.go:169-177) — the reference has no chunk-level dedup.
 //
-// insert:  one thread per chunk — linear probe, atomicCAS on the 8-byte
-//          key prefix, then the full 32-byte digest + chunk address.
+// insert:  one thread per distinct leaf — linear probe, atomicCAS on the
+//          8-byte key prefix, then the full 32-byte digest + chunk address.
 // probe:   one thread per expected chunk — writes the resident source
 //          address (or 0) per chunk.
 // gather:  one 256-thread workgroup per hit chunk — D2D copy at HBM rate.
 //
 // Insert and probe/gather phases are serialized by the engine (host mutex +
-// stream ordering), so entries are never read while half-written.
+// stream ordering), so probe and gather never read a half-written entry.
+// WITHIN one insert launch that does not hold: a lane that loses the CAS to
+// an equal key prefix compares digest_hi while the winner may not have
+// stored it yet (the compiler sinks those stores below the probe loop). The
+// engine therefore hands one launch pairwise distinct digests (it drops
+// repeated leaves on the host, first index kept), so the only answer such a
+// lane can need is "a different digest, keep probing" — which is also what
+// a half-written entry compares as. Entries of earlier launches are
+// complete, so a digest that is already resident is still recognised.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -38,17 +46,20 @@ __device__ inline u64 load_key(const u8* d) {
   return v;
 }
 
-constexpr u32 kMaxProbes = 64;
+constexpr u32 kMaxProbes = modelx::abi::kDedupMaxProbes;
 
-__global__ void dedup_insert_kernel(const u8* __restrict__ leaves, u32 nchunks, u64 base,
+// leaves[i] digests chunk chunk_idx[i] of the blob at `base`; the leaves of
+// one launch are pairwise distinct (see the header comment).
+__global__ void dedup_insert_kernel(const u8* __restrict__ leaves,
+                                    const u32* __restrict__ chunk_idx, u32 nleaves, u64 base,
                                     u64 chunk_size, u64 total, DedupEntry* __restrict__ tab,
                                     u64 cap_mask, u32* __restrict__ dropped) {
   u32 i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= nchunks) return;
+  if (i >= nleaves) return;
   const u8* d = leaves + (u64)i * 32;
   u64 key = load_key(d);
   if (key == 0) return;  // sentinel collision: skip (dedup is best-effort)
-  u64 off = (u64)i * chunk_size;
+  u64 off = (u64)chunk_idx[i] * chunk_size;
   u64 len = total - off < chunk_size ? total - off : chunk_size;
   u64 h = key & cap_mask;
   for (u32 p = 0; p < kMaxProbes; p++) {
@@ -138,14 +149,15 @@ __global__ __launch_bounds__(kGatherThreads) void dedup_gather_kernel(
 
 extern "C" {
 
-hipError_t modelx_dedup_insert(const void* leaves_dev, uint32_t nchunks, uint64_t base,
-                               uint64_t chunk_size, uint64_t total, void* table, uint64_t cap,
+hipError_t modelx_dedup_insert(const void* leaves_dev, const uint32_t* chunk_idx_dev,
+                               uint32_t nleaves, uint64_t base, uint64_t chunk_size,
+                               uint64_t total, void* table, uint64_t cap,
                                uint32_t* dropped_dev, hipStream_t stream) {
-  if (nchunks == 0) return hipSuccess;
-  u32 blocks = (nchunks + 255) / 256;
+  if (nleaves == 0) return hipSuccess;
+  u32 blocks = (nleaves + 255) / 256;
   hipLaunchKernelGGL(dedup_insert_kernel, dim3(blocks), dim3(256), 0, stream,
-                     static_cast<const u8*>(leaves_dev), nchunks, base, chunk_size, total,
-                     static_cast<DedupEntry*>(table), cap - 1, dropped_dev);
+                     static_cast<const u8*>(leaves_dev), chunk_idx_dev, nleaves, base,
+                     chunk_size, total, static_cast<DedupEntry*>(table), cap - 1, dropped_dev);
   return hipGetLastError();
 }
 

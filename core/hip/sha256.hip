@@ -145,11 +145,16 @@ DEV void hash_one_chunk(const uint8_t* __restrict__ data, uint64_t total,
       sha256_compress(st, W);
     }
   } else {
-    const uint32_t* p32 = reinterpret_cast<const uint32_t*>(p);  // 4-aligned (chunk offsets)
+    // any byte phase: a tensor view may start anywhere and a chunk size can
+    // be any integer, so these loads carry no alignment assumption
     for (uint64_t blk = 0; blk < nfull; blk++) {
       uint32_t W[16];
 #pragma unroll
-      for (int i = 0; i < 16; i++) W[i] = bswap(p32[blk * 16 + i]);
+      for (int i = 0; i < 16; i++) {
+        uint32_t w;
+        __builtin_memcpy(&w, p + blk * 64 + i * 4, 4);
+        W[i] = bswap(w);
+      }
       sha256_compress(st, W);
     }
   }

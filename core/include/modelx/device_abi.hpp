@@ -48,6 +48,10 @@ struct ChunkLeavesDesc {
   uint32_t pad_;
 };
 
+// Linear-probe window of the chunk-dedup table (core/hip/dedup.hip): the
+// smallest table capacity the engine accepts.
+constexpr uint32_t kDedupMaxProbes = 64;
+
 }  // namespace abi
 }  // namespace modelx
 
@@ -76,8 +80,11 @@ hipError_t modelx_zstd_compress_frames(const void* src, uint64_t srclen, uint32_
                                        uint64_t stride, void* seq_scratch, uint32_t max_seqs,
                                        int64_t* out_sizes_dev, uint32_t flags,
                                        hipStream_t stream);
-hipError_t modelx_dedup_insert(const void* leaves_dev, uint32_t nchunks, uint64_t base,
-                               uint64_t chunk_size, uint64_t total, void* table, uint64_t cap,
+// leaves_dev: `nleaves` digests, pairwise distinct; chunk_idx_dev[i] is the
+// chunk of the blob that leaf i digests.
+hipError_t modelx_dedup_insert(const void* leaves_dev, const uint32_t* chunk_idx_dev,
+                               uint32_t nleaves, uint64_t base, uint64_t chunk_size,
+                               uint64_t total, void* table, uint64_t cap,
                                uint32_t* dropped_dev, hipStream_t stream);
 hipError_t modelx_dedup_probe(const void* leaves_dev, uint32_t nchunks, uint64_t chunk_size,
                               uint64_t total, const void* table, uint64_t cap,

@@ -36,7 +36,9 @@
 #include <mutex>
 #include <queue>
 #include <stdexcept>
+#include <string_view>
 #include <thread>
+#include <unordered_set>
 #include <vector>
 
 #include "modelx/device_abi.hpp"
@@ -49,6 +51,7 @@ namespace py = pybind11;
 using namespace modelx;
 using modelx::abi::ChunkLeavesDesc;
 using modelx::abi::CopySeg;
+using modelx::abi::kDedupMaxProbes;
 using modelx::abi::PackSeg;
 using modelx::abi::TarEntry;
 using zstdhost::SeekEntry;
@@ -77,6 +80,31 @@ namespace {
 double now_s() {
   return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch())
       .count();
+}
+
+// Leaves a blob of `size` bytes has at `chunk_size` (> 0): an empty blob has
+// the one leaf of the empty string.
+uint64_t expected_leaf_count(uint64_t size, uint64_t chunk_size) {
+  return size ? (size - 1) / chunk_size + 1 : 1;
+}
+
+// Leaf count of a packed 32 B/leaf array, or a throw when it is not the
+// array of a `size`-byte blob at `chunk_size`. The dedup kernels derive
+// every chunk address from (index, chunk_size, size): a surplus leaf would
+// address memory past the blob.
+uint32_t checked_leaf_count(const char* who, size_t leaves_bytes, uint64_t chunk_size,
+                            uint64_t size) {
+  if (chunk_size == 0) throw std::runtime_error(std::string(who) + ": chunk_size is 0");
+  if (leaves_bytes % 32)
+    throw std::runtime_error(std::string(who) + ": leaves length " +
+                             std::to_string(leaves_bytes) + " is not a multiple of 32");
+  uint64_t want = expected_leaf_count(size, chunk_size);
+  if (leaves_bytes / 32 != want || want > UINT32_MAX)
+    throw std::runtime_error(std::string(who) + ": " + std::to_string(leaves_bytes / 32) +
+                             " leaves for " + std::to_string(size) + " bytes at chunk size " +
+                             std::to_string(chunk_size) + " (expected " +
+                             std::to_string(want) + ")");
+  return static_cast<uint32_t>(want);
 }
 
 struct Slot {
@@ -416,8 +444,9 @@ class GpuEngine {
 
   // Chunked-digest leaves of a device buffer; returns leaves as bytes.
   py::bytes sha256_chunk_leaves(uintptr_t dev_ptr, uint64_t size, uint64_t chunk_size) {
+    if (chunk_size == 0) throw std::runtime_error("sha256_chunk_leaves: chunk_size is 0");
     HIP_CHECK(hipSetDevice(device_));
-    uint32_t nchunks = size ? static_cast<uint32_t>((size + chunk_size - 1) / chunk_size) : 1;
+    uint32_t nchunks = static_cast<uint32_t>(expected_leaf_count(size, chunk_size));
     std::string out;
     {
       // temporaries live inside the GIL-released block: hipFree waits for
@@ -941,7 +970,10 @@ class GpuEngine {
     for (size_t i = 0; i < n; i++) {
       auto [ptr, size, cs] = items[i];
       (void)ptr;
-      nchunks[i] = size ? (uint32_t)((size + cs - 1) / cs) : 1;
+      if (cs == 0)
+        throw std::runtime_error("sha256_chunk_leaves_many: chunk_size is 0 (item " +
+                                 std::to_string(i) + ")");
+      nchunks[i] = (uint32_t)expected_leaf_count(size, cs);
       off[i] = total;
       total += nchunks[i];
     }
@@ -988,6 +1020,11 @@ class GpuEngine {
   // registered tensors alive.
 
   void dedup_reset(uint64_t cap_pow2) {
+    // the kernels mask with cap - 1 and probe a window of kDedupMaxProbes
+    if (cap_pow2 && ((cap_pow2 & (cap_pow2 - 1)) || cap_pow2 < kDedupMaxProbes))
+      throw std::runtime_error("dedup_reset: capacity " + std::to_string(cap_pow2) +
+                               " is not a power of two >= " +
+                               std::to_string(kDedupMaxProbes));
     HIP_CHECK(hipSetDevice(device_));
     py::gil_scoped_release release;
     std::lock_guard<std::mutex> lk(dedup_mu_);
@@ -1009,8 +1046,27 @@ class GpuEngine {
   uint32_t dedup_register(py::bytes leaves, uintptr_t base, uint64_t chunk_size,
                           uint64_t total) {
     std::string lv = leaves;
+    uint32_t nleaves = checked_leaf_count("dedup_register", lv.size(), chunk_size, total);
     HIP_CHECK(hipSetDevice(device_));
     py::gil_scoped_release release;
+    // Repeated leaves (zero-filled tensors, padding) are dropped here, first
+    // index kept: every key of one insert launch is then distinct, so a
+    // lane that loses the CAS never has to read the winner's payload to
+    // recognise its own digest (see dedup.hip).
+    std::string uniq;
+    std::vector<uint32_t> idx;
+    {
+      std::unordered_set<std::string_view> seen;
+      seen.reserve(nleaves);
+      idx.reserve(nleaves);
+      for (uint32_t i = 0; i < nleaves; i++)
+        if (seen.insert(std::string_view(lv.data() + (size_t)i * 32, 32)).second)
+          idx.push_back(i);
+      uniq.reserve(idx.size() * 36);
+      for (uint32_t i : idx) uniq.append(lv.data() + (size_t)i * 32, 32);
+      uniq.append(reinterpret_cast<const char*>(idx.data()), idx.size() * 4);
+    }
+    uint32_t n = static_cast<uint32_t>(idx.size());
     std::lock_guard<std::mutex> lk(dedup_mu_);
     if (!dedup_table_) {
       // lazy init at default capacity
@@ -1021,12 +1077,14 @@ class GpuEngine {
       dedup_dropped_ = DeviceBuffer(sizeof(uint32_t));
       HIP_CHECK(hipMemsetAsync(dedup_dropped_.get(), 0, sizeof(uint32_t), hash_stream_));
     }
-    uint32_t n = static_cast<uint32_t>(lv.size() / 32);
-    void* dleaves = ds_leaves_.reserve(lv.size() ? lv.size() : 32);
-    HIP_CHECK(hipMemcpyAsync(dleaves, lv.data(), lv.size(), hipMemcpyHostToDevice,
+    // one upload: n leaves (32 B each), then their n chunk indexes
+    char* dleaves = ds_leaves_.reserve<char>(uniq.size());
+    HIP_CHECK(hipMemcpyAsync(dleaves, uniq.data(), uniq.size(), hipMemcpyHostToDevice,
                              hash_stream_));
-    HIP_CHECK(modelx_dedup_insert(dleaves, n, base, chunk_size, total, dedup_table_.get(),
-                                  dedup_cap_, dedup_dropped_.get<uint32_t>(), hash_stream_));
+    const uint32_t* didx = reinterpret_cast<const uint32_t*>(dleaves + (size_t)n * 32);
+    HIP_CHECK(modelx_dedup_insert(dleaves, didx, n, base, chunk_size, total,
+                                  dedup_table_.get(), dedup_cap_,
+                                  dedup_dropped_.get<uint32_t>(), hash_stream_));
     uint32_t dropped = 0;
     HIP_CHECK(hipStreamSynchronize(hash_stream_));
     HIP_CHECK(hipMemcpy(&dropped, dedup_dropped_.get(), sizeof dropped, hipMemcpyDeviceToHost));
@@ -1038,10 +1096,12 @@ class GpuEngine {
   py::tuple dedup_pull(py::bytes expect, uintptr_t dst_ptr, uint64_t chunk_size,
                        uint64_t total) {
     std::string lv = expect;
-    uint32_t n = static_cast<uint32_t>(lv.size() / 32);
+    // the gather kernel writes chunk i at dst_ptr + i * chunk_size: a leaf
+    // past the blob's end would be a write past the destination
+    uint32_t n = checked_leaf_count("dedup_pull", lv.size(), chunk_size, total);
     std::vector<std::pair<uint64_t, uint64_t>> missing;
     uint64_t deduped = 0;
-    if (n && dedup_table_) {
+    if (total && dedup_table_) {
       HIP_CHECK(hipSetDevice(device_));
       py::gil_scoped_release release;
       std::lock_guard<std::mutex> lk(dedup_mu_);
@@ -1059,7 +1119,6 @@ class GpuEngine {
       for (uint32_t i = 0; i < n; i++) {
         uint64_t off = (uint64_t)i * chunk_size;
         uint64_t ln = total - off < chunk_size ? total - off : chunk_size;
-        if (ln == 0) break;
         if (haddr[i] != 0) {
           deduped += ln;
         } else if (!missing.empty() && missing.back().first + missing.back().second == off) {

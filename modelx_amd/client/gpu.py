@@ -63,6 +63,37 @@ def _tls_verify() -> bool:
     return True
 
 
+def leaves_usable(leaves, size: int, chunk_size) -> bool:
+    """Whether ``leaves`` is the packed 32 B/leaf array of a ``size``-byte
+    blob at ``chunk_size``: a positive integer chunk size and exactly one
+    leaf per chunk (one leaf for an empty blob). Leaves and the chunk size
+    arrive from the remote; the device kernels address chunk ``i`` at
+    ``i * chunk_size``, so a leaf too many is a write past the tensor.
+    Callers treat unusable leaves like a missing sidecar."""
+    if isinstance(chunk_size, bool) or not isinstance(chunk_size, int) or chunk_size <= 0:
+        return False
+    if not isinstance(leaves, (bytes, bytearray, memoryview)):
+        return False
+    if isinstance(size, bool) or not isinstance(size, int) or size < 0:
+        return False
+    want = (size - 1) // chunk_size + 1 if size else 1
+    return len(leaves) == 32 * want
+
+
+def _annotated_chunk_size(desc: types.Descriptor) -> int:
+    """The chunk-size annotation as a positive integer, or 0 when it is
+    absent or anything else (the caller then falls back as for an absent
+    one)."""
+    note = desc.annotations.get(types.ANNOTATION_CHUNK_SIZE, "")
+    if isinstance(note, bool):
+        return 0
+    if isinstance(note, int):
+        return note if note > 0 else 0
+    if isinstance(note, str) and note.isascii() and note.isdigit():
+        return int(note)
+    return 0
+
+
 def _signed_headers(part: dict) -> Dict[str, str]:
     out = {}
     for k, v in (part.get("signedHeader") or {}).items():
@@ -236,7 +267,14 @@ class GpuClient:
     @staticmethod
     def _bad_chunk_ranges(got: bytes, expect: bytes, chunk_size: int,
                           size: int) -> List[Tuple[int, int]]:
-        """Contiguous (offset, length) ranges of mismatching chunks."""
+        """Contiguous (offset, length) ranges of mismatching chunks, all
+        inside ``[0, size)``. Leaves that are not the array of a
+        ``size``-byte blob at ``chunk_size`` say nothing about any chunk:
+        the whole blob is then bad."""
+        if not leaves_usable(expect, size, chunk_size) or len(got) != len(expect):
+            return [(0, size)] if size > 0 else []
+        if size == 0:
+            return []  # the one leaf of an empty blob covers no bytes
         n = len(expect) // 32
         bad = [i for i in range(n) if got[i * 32 : (i + 1) * 32] != expect[i * 32 : (i + 1) * 32]]
         ranges: List[Tuple[int, int]] = []
@@ -251,12 +289,18 @@ class GpuClient:
 
     # ------------------------------------------------------ chunk dedup --
 
-    def register_chunks(self, tensor, leaves: bytes, chunk_size: int) -> None:
+    def register_chunks(self, tensor, leaves: bytes, chunk_size: int,
+                        size: Optional[int] = None) -> None:
         """Add a blob's chunks to the HBM dedup table (dedup.hip insert
-        kernel); keeps the tensor alive while registered."""
+        kernel); keeps the tensor alive while registered. ``size`` is the
+        blob's length when the tensor is larger than the blob it holds."""
         if not self.dedup:
             return
-        size = tensor.numel() * tensor.element_size()
+        nbytes = tensor.numel() * tensor.element_size()
+        if size is None:
+            size = nbytes
+        if size > nbytes or not leaves_usable(leaves, size, chunk_size):
+            return  # would index chunks the tensor does not have
         self._dedup_tensors.append(tensor)
         self.engine.dedup_register(leaves, tensor.data_ptr(), chunk_size, size)
         self._dedup_registered = True
@@ -374,11 +418,16 @@ class GpuClient:
             return tensor
         url, headers = located
 
-        def expected_leaves():
-            return (self._plan_leaves(plan_entry, desc)
-                    or self._expected_leaves(repository, desc))
-        cs = int(desc.annotations.get(types.ANNOTATION_CHUNK_SIZE, 0) or 0) or (
+        cs = _annotated_chunk_size(desc) or (
             dg.algo_chunk_size(desc.digest.split(":", 1)[0]) or DEFAULT_GPU_CHUNK)
+
+        def expected_leaves():
+            # the sidecar's own digest says nothing about its length: leaves
+            # that do not fit (size, cs) count as no leaves at all, so the
+            # pull degrades to the full, digest-verified fetch
+            lv = (self._plan_leaves(plan_entry, desc)
+                  or self._expected_leaves(repository, desc))
+            return lv if lv is not None and leaves_usable(lv, desc.size, cs) else None
 
         if resume and had_tensor:
             expect = expected_leaves()
@@ -444,7 +493,7 @@ class GpuClient:
                             raise er.ModelxError(
                                 er.ErrCode.DIGEST_INVALID,
                                 f"GPU chunk digest mismatch for {desc.name}: {root}")
-                    self.register_chunks(tensor, expect, cs)
+                    self.register_chunks(tensor, expect, cs, desc.size)
                     return tensor
 
         # streaming-hash path: chunks are hashed on each slot's stream right
@@ -468,7 +517,7 @@ class GpuClient:
             if got == expect_digest:
                 self.last_stats.append({"phase": "pull-verify", "bytes": desc.size,
                                         "seconds": time.monotonic() - t0 - stats["seconds"]})
-                self.register_chunks(tensor, leaves, cs)
+                self.register_chunks(tensor, leaves, cs, desc.size)
                 return tensor
             # fall through to the refetch path below
         else:
@@ -771,8 +820,7 @@ class GpuClient:
 
         # verify the stored (compressed) bytes while streaming
         chunk_note = desc.annotations.get(types.ANNOTATION_CHUNK_DIGEST, "")
-        cs = int(desc.annotations.get(types.ANNOTATION_CHUNK_SIZE, 0) or 0) or \
-            dg.DEFAULT_CHUNK_SIZE
+        cs = _annotated_chunk_size(desc) or dg.DEFAULT_CHUNK_SIZE
         hasher = dg.StreamingDigester(chunk_size=cs)
 
         inflater = zlib.decompressobj(16 + zlib.MAX_WBITS)  # gzip framing

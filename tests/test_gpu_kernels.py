@@ -72,6 +72,64 @@ class TestSha256Kernels:
         for i, raw in enumerate(raws):
             assert digests[i * 32 : (i + 1) * 32] == hashlib.sha256(raw).digest()
 
+    # The kernels load 16 bytes at a time only from a 16-byte-aligned chunk;
+    # any other base or chunk size takes the exact-width branch. A view may
+    # start at any byte of an allocation and a chunk size may be any integer.
+    UNALIGNED_SIZE = 200 * 1024 + 37  # 37-byte tail behind the last 64 B block
+
+    @pytest.fixture(scope="class")
+    def unaligned(self):
+        """(host bytes, device tensor) shared by the unaligned cases."""
+        g = torch.Generator().manual_seed(11)
+        data = torch.randint(0, 256, (self.UNALIGNED_SIZE + 16,), dtype=torch.uint8,
+                             generator=g)
+        dev = data.cuda()
+        torch.cuda.synchronize()
+        return data.numpy().tobytes(), dev
+
+    @pytest.mark.parametrize("cs", [64, 65, 1000, 4100, 65536])
+    def test_chunk_leaves_any_base_phase(self, engine, unaligned, cs):
+        raw, dev = unaligned
+        size = self.UNALIGNED_SIZE
+        expect = [b"".join(dg.chunk_leaves(raw[off : off + size], cs)) for off in range(16)]
+        for off in range(16):
+            got = engine.sha256_chunk_leaves(dev.data_ptr() + off, size, cs)
+            assert got == expect[off], f"base phase {off}"
+        many = engine.sha256_chunk_leaves_many(
+            [(dev.data_ptr() + off, size, cs) for off in range(16)])
+        for off in range(16):
+            assert many[off] == expect[off], f"base phase {off} (batched)"
+
+    def test_leaves_many_mixed_buffers(self, engine, unaligned):
+        """One batched call over different chunk sizes and base phases, with
+        an empty buffer in the middle and another one last; more than 256
+        chunks, so the per-lane buffer search crosses a workgroup."""
+        raw, dev = unaligned
+        shapes = [(0, 70000, 1000), (3, 4100, 4100), (7, 0, 64), (1, 20000, 65),
+                  (16, 64, 64), (9, 100000, 65536), (5, 12345, 4096), (2, 0, 1000)]
+        assert sum(max(1, -(-size // cs)) for _, size, cs in shapes) > 256
+        got = engine.sha256_chunk_leaves_many(
+            [(dev.data_ptr() + off, size, cs) for off, size, cs in shapes])
+        assert len(got) == len(shapes)
+        for (off, size, cs), leaves in zip(shapes, got):
+            assert leaves == b"".join(dg.chunk_leaves(raw[off : off + size], cs)), \
+                (off, size, cs)
+
+    def test_multibuf_any_base_phase(self, engine, unaligned):
+        raw, dev = unaligned
+        lengths = [0, 55, 56, 64, 119, 120, 4099]
+        cases = [(off, n) for off in range(16) for n in lengths]
+        # other content per buffer: each starts `stride` (a multiple of 16,
+        # so `off` stays the base phase) after the last
+        stride = 1616
+        bufs = [(dev.data_ptr() + k * stride + off, n) for k, (off, n) in enumerate(cases)]
+        assert (len(cases) - 1) * stride + 15 + 4099 <= self.UNALIGNED_SIZE
+        digests = engine.sha256_multibuf(bufs)
+        for k, (off, n) in enumerate(cases):
+            start = k * stride + off
+            assert digests[k * 32 : (k + 1) * 32] == \
+                hashlib.sha256(raw[start : start + n]).digest(), (off, n)
+
 
 class TestEngineTransfers:
     @pytest.fixture(scope="class")
