@@ -92,5 +92,11 @@ hipError_t modelx_dedup_probe(const void* leaves_dev, uint32_t nchunks, uint64_t
 hipError_t modelx_dedup_gather(const uint64_t* src_addr_dev, const uint64_t* src_len_dev,
                                uint32_t nchunks, uint64_t dst_base, uint64_t chunk_size,
                                hipStream_t stream);
+// Byte-plane split (merge == 0) or merge of `size` bytes, src -> dst, which
+// must not overlap (modelx/byteplane_host.hpp defines the transform).
+// hipErrorInvalidValue unless elem is 2, 4 or 8 and group a positive
+// multiple of it.
+hipError_t modelx_byte_planes(const void* src, void* dst, uint64_t size, uint32_t elem,
+                              uint64_t group, int merge, hipStream_t stream);
 
 }  // extern "C"

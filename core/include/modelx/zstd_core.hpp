@@ -45,6 +45,8 @@ static const u32 kMagic = 0xFD2FB528u;
 static const u32 kMagicSkippableSeek = 0x184D2A5Eu;  // seekable-format skippable frame
 static const u32 kSeekTableMagic = 0x8F92EAB1u;
 static const u32 kBlockMax = 128 * 1024;
+// EncTables::flags bit 2 (zstd_enc.hpp): literals-only encode, no LZ parse
+static const u32 kEncLiteralsOnly = 4;
 
 // error codes (returned negative from decode/encode entry points)
 enum {

@@ -720,7 +720,11 @@ MX_HD static inline i64 emit_huf_literals(const HufEnc* e, const u8* lit, u64 n,
 // LDS on the GPU so the redundant-wavefront execution doesn't spill
 // per-lane copies; the histogram is filled with LDS atomics).
 struct EncTables {
-  u32 flags;  // bit0: disable the lane-parallel huffman stream encoder
+  // bit0: disable the lane-parallel huffman stream encoder
+  // bit2 (value 4): literals-only — skip the LZ parse, so every block is an
+  // RLE block, a Huffman-literals block or raw (for byte planes of dense
+  // float data, where short matches cost more as sequences than as literals)
+  u32 flags;
   FseEnc ell, eof, eml;
   FseEnc wfse;  // huffman-weight FSE encoder (full-byte alphabets)
   HufEnc he;
@@ -751,7 +755,9 @@ MX_HD static inline i64 encode_block(const u8* src, u64 block_off, u64 block_len
   if (dstcap < raw_total) return MXZ_ERR_DST_SMALL;
 
   u64 lit_total = 0;
-  u32 nseq = lz_parse(src, block_off, block_len, hash, seqs, max_seqs, &lit_total);
+  u32 nseq = (et->flags & kEncLiteralsOnly)
+                 ? 0
+                 : lz_parse(src, block_off, block_len, hash, seqs, max_seqs, &lit_total);
 
   u64 csize = 0;
   bool use_raw = false;

@@ -51,7 +51,9 @@ std::vector<SeekEntry> walk_frames(const uint8_t* blob, size_t len);
 std::vector<uint8_t> build_seek_table(const std::vector<SeekEntry>& entries);
 
 // CPU compress src into a seekable multi-frame blob (threads over frames).
-std::vector<uint8_t> compress_seekable(const uint8_t* src, size_t len, uint32_t frame_raw);
+// `flags` are EncTables::flags (zstd_enc.hpp): 4 = literals-only.
+std::vector<uint8_t> compress_seekable(const uint8_t* src, size_t len, uint32_t frame_raw,
+                                       uint32_t flags = 0);
 
 // CPU decompress a seekable (or plain multi-frame) blob.
 // Returns decompressed bytes; throws std::runtime_error on corrupt input.

@@ -41,6 +41,7 @@
 #include <unordered_set>
 #include <vector>
 
+#include "modelx/byteplane_host.hpp"
 #include "modelx/device_abi.hpp"
 #include "modelx/http.hpp"
 #include "modelx/tar_host.hpp"
@@ -58,7 +59,9 @@ using zstdhost::SeekEntry;
 
 // MODELX_ZSTD_FLAGS: bit0 disables the lane-parallel huffman encoder,
 // bit1 disables the wave-split literal-stream decoder (bisection/panic
-// switches for the device codec).
+// switches for the device codec); bit2 (value 4) makes every compress
+// literals-only (no LZ parse) — zstd_compress_device(literals_only=true) sets
+// it for one launch, which is how byte-plane blobs are encoded.
 static uint32_t zstd_flags() {
   static uint32_t f = [] {
     const char* v = getenv("MODELX_ZSTD_FLAGS");
@@ -758,16 +761,59 @@ class GpuEngine {
     return lay.total;
   }
 
+  // ------------------------------------------------------ byte planes ----
+
+  // Byte-plane split (merge=false) or merge (merge=true) of device buffers
+  // (core/hip/byteplane.hip; the transform is byteplane_host.hpp's).
+  // items = [(src_ptr, dst_ptr, size, elem, group)]. Every item is checked
+  // before the first launch; then all launch on hash_stream_ with ONE sync
+  // (the batching rule of zstd_decompress_many). size == 0 is a no-op.
+  void byte_planes(
+      const std::vector<std::tuple<uintptr_t, uintptr_t, uint64_t, uint64_t, uint64_t>>& items,
+      bool merge) {
+    for (size_t i = 0; i < items.size(); i++) {
+      auto [src, dst, size, elem, group] = items[i];
+      try {
+        byteplane::validate(elem, group);
+      } catch (const std::invalid_argument& e) {
+        throw std::runtime_error(std::string(e.what()) + " (item " + std::to_string(i) + ")");
+      }
+      if (size == 0) continue;
+      if (src > UINTPTR_MAX - size || dst > UINTPTR_MAX - size)
+        throw std::runtime_error("byte planes: item " + std::to_string(i) +
+                                 " wraps the address space");
+      if (src < dst + size && dst < src + size)
+        throw std::runtime_error("byte planes: source and destination of item " +
+                                 std::to_string(i) + " overlap");
+    }
+    HIP_CHECK(hipSetDevice(device_));
+    py::gil_scoped_release release;
+    bool launched = false;
+    for (auto& [src, dst, size, elem, group] : items) {
+      if (size == 0) continue;
+      HIP_CHECK(modelx_byte_planes(reinterpret_cast<const void*>(src),
+                                   reinterpret_cast<void*>(dst), size,
+                                   static_cast<uint32_t>(elem), group, merge ? 1 : 0,
+                                   hash_stream_));
+      launched = true;
+    }
+    if (launched) HIP_CHECK(hipStreamSynchronize(hash_stream_));
+  }
+
   // ------------------------------------------------------------- zstd ----
 
   // Compress a device buffer into a seekable multi-frame zstd blob at
   // dst_ptr (device). Returns the total blob size (frames + seek table).
   // One workgroup per frame (core/hip/zstd.hip); frames are compressed into
   // padded per-frame scratch in batches, packed with the scatter kernel,
-  // and the seek table is appended from the host.
+  // and the seek table is appended from the host. literals_only skips the LZ
+  // parse (EncTables::flags bit 2): right for byte planes of dense float
+  // data, worse on mostly-zero data, where Huffman cannot go below one bit
+  // per byte.
   uint64_t zstd_compress_device(uintptr_t src_ptr, uint64_t size, uint32_t frame_raw,
-                                uintptr_t dst_ptr, uint64_t dst_cap) {
+                                uintptr_t dst_ptr, uint64_t dst_cap, bool literals_only) {
     HIP_CHECK(hipSetDevice(device_));
+    const uint32_t flags = zstd_flags() | (literals_only ? zstd::kEncLiteralsOnly : 0u);
     if (frame_raw == 0) frame_raw = 128 << 10;
     using namespace modelx::zstd;
     uint64_t nframes = size ? (size + frame_raw - 1) / frame_raw : 1;
@@ -788,7 +834,7 @@ class GpuEngine {
       uint32_t n = (uint32_t)std::min<uint64_t>(batch, nframes - first);
       HIP_CHECK(modelx_zstd_compress_frames(reinterpret_cast<void*>(src_ptr), size, frame_raw,
                                             (uint32_t)first, n, dscratch, stride, dseqs,
-                                            max_seqs, dsizes, zstd_flags(), hash_stream_));
+                                            max_seqs, dsizes, flags, hash_stream_));
       HIP_CHECK(hipStreamSynchronize(hash_stream_));
       HIP_CHECK(hipMemcpy(hsizes.data(), dsizes, n * sizeof(int64_t), hipMemcpyDeviceToHost));
       for (uint32_t i = 0; i < n; i++) {
@@ -1341,7 +1387,9 @@ PYBIND11_MODULE(_core, m) {
       .def("sha256_chunk_leaves_many", &GpuEngine::sha256_chunk_leaves_many,
            py::arg("items"))
       .def("zstd_compress_device", &GpuEngine::zstd_compress_device, py::arg("src_ptr"),
-           py::arg("size"), py::arg("frame_raw"), py::arg("dst_ptr"), py::arg("dst_cap"))
+           py::arg("size"), py::arg("frame_raw"), py::arg("dst_ptr"), py::arg("dst_cap"),
+           py::arg("literals_only") = false)
+      .def("byte_planes", &GpuEngine::byte_planes, py::arg("items"), py::arg("merge"))
       .def("zstd_decompress_device", &GpuEngine::zstd_decompress_device, py::arg("src_ptr"),
            py::arg("src_len"), py::arg("dst_ptr"), py::arg("dst_cap"))
       .def("synchronize", &GpuEngine::synchronize);
@@ -1375,17 +1423,38 @@ PYBIND11_MODULE(_core, m) {
   // CPU client for +zstd blobs and by tests as the GPU-vs-CPU oracle.
   m.def(
       "zstd_compress_cpu",
-      [](py::bytes data, uint32_t frame_raw) {
+      [](py::bytes data, uint32_t frame_raw, bool literals_only) {
         std::string s = data;
         std::vector<uint8_t> out;
         {
           py::gil_scoped_release release;
           out = zstdhost::compress_seekable(reinterpret_cast<const uint8_t*>(s.data()),
-                                            s.size(), frame_raw);
+                                            s.size(), frame_raw,
+                                            literals_only ? zstd::kEncLiteralsOnly : 0u);
         }
         return py::bytes(reinterpret_cast<const char*>(out.data()), out.size());
       },
-      py::arg("data"), py::arg("frame_raw") = (uint32_t)(128 << 10));
+      py::arg("data"), py::arg("frame_raw") = (uint32_t)(128 << 10),
+      py::arg("literals_only") = false);
+  // The byte-plane transform's host model (byteplane_host.hpp): split
+  // (merge=False) or merge of `data` at element size `elem` and group size
+  // `group`. The CPU client's codec filter and the GPU kernels' oracle.
+  m.def(
+      "byte_planes_cpu",
+      [](py::bytes data, uint64_t elem, uint64_t group, bool merge) {
+        byteplane::validate(elem, group);
+        std::string s = data;
+        std::string out(s.size(), '\0');
+        {
+          py::gil_scoped_release release;
+          const uint8_t* src = reinterpret_cast<const uint8_t*>(s.data());
+          uint8_t* dst = reinterpret_cast<uint8_t*>(&out[0]);
+          if (merge) byteplane::merge(src, dst, s.size(), static_cast<uint32_t>(elem), group);
+          else byteplane::split(src, dst, s.size(), static_cast<uint32_t>(elem), group);
+        }
+        return py::bytes(out);
+      },
+      py::arg("data"), py::arg("elem"), py::arg("group"), py::arg("merge") = false);
   // One-shot GET through the NATIVE http client (the exact code path the
   // engine's ranged fetches use, incl. TLS) — lets the GPU-less suite prove
   // https presigned-URL support against a TLS server.

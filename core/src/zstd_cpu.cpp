@@ -185,7 +185,8 @@ std::vector<uint8_t> build_seek_table(const std::vector<SeekEntry>& entries) {
   return out;
 }
 
-std::vector<uint8_t> compress_seekable(const uint8_t* src, size_t len, uint32_t frame_raw) {
+std::vector<uint8_t> compress_seekable(const uint8_t* src, size_t len, uint32_t frame_raw,
+                                       uint32_t flags) {
   if (frame_raw == 0) frame_raw = 128 * 1024;
   size_t nframes = len ? (len + frame_raw - 1) / frame_raw : 1;
   // worst case: raw blocks + frame overhead
@@ -203,7 +204,7 @@ std::vector<uint8_t> compress_seekable(const uint8_t* src, size_t len, uint32_t 
       std::vector<u32> hash(1u << kHashLog);
       std::vector<Seq> seqs(kBlockMax / 4 + 1);
       EncTables et;
-      et.flags = 0;
+      et.flags = flags;
       enc_tables_init(&et);
       size_t i;
       while ((i = next.fetch_add(1)) < nframes) {

@@ -55,11 +55,15 @@ def cmd_init(args) -> int:
 
 
 def cmd_push(args) -> int:
+    from ..client.push import check_planes
+
+    check_planes(args.planes, args.compress)  # before anything is contacted
     ref, client = _client_for(args.ref, args.insecure)
     if not ref.version:
         ref.version = "latest"
     manifest = client.push(ref.repository, ref.version, args.dir, configfile=args.config,
-                           digest_mode=args.digest_mode, compress=args.compress)
+                           digest_mode=args.digest_mode, compress=args.compress,
+                           planes=args.planes)
     total = manifest.config.size + sum(b.size for b in manifest.blobs)
     print(f"pushed {ref.repository}@{ref.version}: {len(manifest.blobs)} blobs, "
           f"{human_size(total)}")
@@ -227,6 +231,10 @@ def build_parser() -> argparse.ArgumentParser:
     sp.add_argument("--compress", choices=["", "zstd"], default="",
                     help="store file blobs zstd-compressed (seekable multi-frame, "
                          "GPU-parallel decode)")
+    sp.add_argument("--planes", type=int, choices=[0, 2, 4, 8], default=0,
+                    help="with --compress zstd: store the byte planes of files made of "
+                         "elements this many bytes wide (2 for bf16/fp16, 4 for fp32); "
+                         "smaller blobs for dense float weights")
     sp.set_defaults(fn=cmd_push)
 
     sp = sub.add_parser("pull", help="pull a model version")

@@ -24,10 +24,13 @@ class Client:
     def push(self, repository: str, version: str, basedir: str,
              configfile: str = "modelx.yaml", digest_mode: str = "sha256",
              quiet: Optional[bool] = None, dir_format: str = "tar+gz",
-             compress: str = "") -> types.Manifest:
+             compress: str = "", planes: int = 0) -> types.Manifest:
+        """``planes`` = 2, 4 or 8 (with ``compress="zstd"``) stores each file's
+        byte planes for that element size: smaller +zstd blobs for dense
+        float weights."""
         return self.pusher.push(repository, version or "latest", basedir, configfile,
                                 digest_mode=digest_mode, quiet=quiet, dir_format=dir_format,
-                                compress=compress)
+                                compress=compress, planes=planes)
 
     def pull(self, repository: str, version: str, into_dir: str,
              quiet: Optional[bool] = None) -> types.Manifest:

@@ -25,6 +25,7 @@ from typing import Dict, List, Optional, Tuple
 from ..wire import digest as dg
 from ..wire import errors as er
 from ..wire import types
+from .push import check_planes
 from .registry import RegistryClient
 
 DEFAULT_SLOT_BYTES = 64 << 20
@@ -324,11 +325,17 @@ class GpuClient:
         SHA-256 verify over the stored bytes), decode every frame in its own
         workgroup (core/hip/zstd.hip), then GPU-verify the uncompressed
         chunked digest from the raw-digest annotation. The whole path —
-        transfer, hash, inflate, re-hash — never leaves the GPU."""
+        transfer, hash, inflate, re-hash — never leaves the GPU.
+
+        A blob with the byte-planes annotation decodes into a temporary,
+        the merge kernel (core/hip/byteplane.hip) rebuilds the interleaved
+        bytes, and only those are checked against the raw digest. A
+        malformed annotation is refused before anything is fetched."""
         import time
 
         import torch
 
+        planes = types.parse_byte_planes(desc.annotations.get(types.ANNOTATION_BYTE_PLANES))
         comp = self.pull_blob_to_device(repository, desc, verify=verify,
                                         plan_entry=plan_entry)
         raw_size = int(desc.annotations.get(types.ANNOTATION_RAW_SIZE, 0) or 0)
@@ -374,6 +381,9 @@ class GpuClient:
             raise er.ModelxError(er.ErrCode.DIGEST_INVALID,
                                  f"zstd size mismatch for {desc.name}: {got} != {raw_size}")
         out = out[:got]
+        if planes:
+            del comp  # the planar temporary and the result are the residents now
+            out = self._merge_byte_planes([(out, planes)])[0]
         raw_digest = desc.annotations.get(types.ANNOTATION_RAW_DIGEST, "")
         if verify and raw_digest:
             cs = dg.algo_chunk_size(raw_digest.split(":", 1)[0]) or DEFAULT_GPU_CHUNK
@@ -383,6 +393,26 @@ class GpuClient:
                 raise er.ModelxError(er.ErrCode.DIGEST_INVALID,
                                      f"uncompressed digest mismatch for {desc.name}")
         return out
+
+    def _merge_byte_planes(self, jobs) -> List["torch.Tensor"]:
+        """Planar tensors back to interleaved bytes: jobs = [(planar uint8
+        tensor, (E, G))]; ONE engine call (one stream sync) for the whole
+        list, one ``pull-byte-planes-merge`` entry in ``last_stats``."""
+        import time
+
+        import torch
+
+        t0 = time.monotonic()
+        outs = [torch.empty(max(p.numel(), 1), dtype=torch.uint8,
+                            device=f"cuda:{self.device}")[:p.numel()] for p, _ in jobs]
+        self.engine.byte_planes(
+            [(p.data_ptr(), o.data_ptr(), p.numel(), elem, group)
+             for (p, (elem, group)), o in zip(jobs, outs)], True)
+        self.last_stats.append({"phase": "pull-byte-planes-merge",
+                                "bytes": sum(p.numel() for p, _ in jobs),
+                                "blobs": len(jobs),
+                                "seconds": time.monotonic() - t0})
+        return outs
 
     def pull_blob_to_device(self, repository: str, desc: types.Descriptor,
                             tensor=None, verify: bool = True,
@@ -578,6 +608,11 @@ class GpuClient:
 
         import torch
 
+        # byte-plane annotations, parsed (and a malformed one refused) before
+        # anything is fetched; planar blobs decode into a temporary and ONE
+        # merge call per batch rebuilds the interleaved bytes
+        plane_of = {key: types.parse_byte_planes(
+            desc.annotations.get(types.ANNOTATION_BYTE_PLANES)) for key, desc, _ in jobs}
         wave_cap = self.ZSTD_WAVE_CAP
         if len(jobs) > 1:
             total_raw = sum(int(d.annotations.get(types.ANNOTATION_RAW_SIZE, 0) or 0)
@@ -634,6 +669,14 @@ class GpuClient:
                                      f"zstd size mismatch for {desc.name}: "
                                      f"{got} != {raw_size}")
             outs[key] = outs[key][:got]
+        del comp, items  # decoded: the compressed tensors can go
+        planar = [(key, plane_of[key]) for key, _, _ in metas if plane_of[key]]
+        if planar:
+            # ONE merge call for the batch, before the raw digests are
+            # checked: those describe the interleaved bytes
+            merged = self._merge_byte_planes([(outs[key], pl) for key, pl in planar])
+            for (key, _), t in zip(planar, merged):
+                outs[key] = t
         if verify:
             vitems, vmeta = [], []
             for key, desc, raw_size in metas:
@@ -1066,13 +1109,27 @@ class GpuClient:
                       chunk_size: int = DEFAULT_GPU_CHUNK,
                       part_bytes: int = DEFAULT_PART_BYTES,
                       compress: str = "", digest_mode: str = "chunked",
-                      dirs: Optional[Dict[str, Dict[str, "torch.Tensor"]]] = None
-                      ) -> types.Manifest:
+                      dirs: Optional[Dict[str, Dict[str, "torch.Tensor"]]] = None,
+                      planes=0) -> types.Manifest:
         """Digest on GPU → presigned multipart upload → manifest PUT last.
         With ``compress="zstd"`` each tensor is compressed on-GPU into a
         seekable multi-frame zstd blob (core/hip/zstd.hip) first; the
         descriptor digest covers the stored (compressed) bytes and the
         raw-digest/raw-size annotations carry the uncompressed identity.
+
+        ``planes`` (only with ``compress="zstd"``) is 0, an element size 2, 4
+        or 8, or ``"auto"`` (each tensor's ``element_size()`` when that is 2,
+        4 or 8, otherwise 0). A tensor pushed with planes is split on-GPU
+        into one plane per byte position of its element
+        (core/hip/byteplane.hip, groups of E × 128 KiB so every zstd frame
+        holds one plane), compressed literals-only, and its descriptor gets
+        the byte-planes annotation; raw-digest and raw-size still describe
+        the tensor's own bytes. Dense float weights store smaller this way
+        (profiles/byte_planes.md); mostly-zero tensors store larger, because
+        literals-only coding cannot go below one bit per byte. While such a
+        tensor is compressed HBM holds the source, its planar copy and the
+        compress bound (about three times the tensor); the planar copy is
+        freed before the upload.
 
         ``digest_mode="sha256"`` makes the main descriptor digest the
         wire-canonical plain sha256 (reference push.go:149-161 semantics —
@@ -1099,6 +1156,10 @@ class GpuClient:
         if digest_mode not in ("chunked", "sha256"):
             raise er.ModelxError(er.ErrCode.UNSUPPORTED,
                                  f"unknown digest_mode {digest_mode!r}")
+        if planes != "auto":
+            check_planes(planes, compress)
+        elif compress != "zstd":
+            check_planes(2, compress)  # any planes without zstd: UNSUPPORTED
         dir_names = set()
         if dirs:
             if compress:
@@ -1227,15 +1288,35 @@ class GpuClient:
                 bound = core.zstd_compress_bound(size)
                 comp_keep = torch.empty(bound, dtype=torch.uint8,
                                         device=f"cuda:{self.device}")
+                elem = planes
+                if planes == "auto":
+                    elem = t.element_size() if t.element_size() in \
+                        types.BYTE_PLANES_ELEMS else 0
+                src_ptr, planar = t.data_ptr(), None
+                extra_notes = {types.ANNOTATION_RAW_DIGEST: raw_root,
+                               types.ANNOTATION_RAW_SIZE: str(size)}
+                if elem:
+                    group = elem * types.BYTE_PLANES_FRAME
+                    t0 = time.monotonic()
+                    planar = torch.empty(size, dtype=torch.uint8,
+                                         device=f"cuda:{self.device}")
+                    self.engine.byte_planes(
+                        [(t.data_ptr(), planar.data_ptr(), size, elem, group)], False)
+                    self.last_stats.append({"phase": "push-byte-planes-split",
+                                            "bytes": size,
+                                            "seconds": time.monotonic() - t0})
+                    src_ptr = planar.data_ptr()
+                    extra_notes[types.ANNOTATION_BYTE_PLANES] = \
+                        types.format_byte_planes(elem, group)
                 t0 = time.monotonic()
                 comp_size = self.engine.zstd_compress_device(
-                    t.data_ptr(), size, 128 << 10, comp_keep.data_ptr(), bound)
+                    src_ptr, size, types.BYTE_PLANES_FRAME, comp_keep.data_ptr(), bound,
+                    literals_only=bool(elem))
+                del planar
                 self.last_stats.append({"phase": "push-zstd-compress", "bytes": size,
                                         "seconds": time.monotonic() - t0,
                                         "compressed": comp_size})
                 media_type = types.MEDIA_TYPE_MODEL_FILE_ZSTD
-                extra_notes = {types.ANNOTATION_RAW_DIGEST: raw_root,
-                               types.ANNOTATION_RAW_SIZE: str(size)}
                 push_ptr, push_size = comp_keep.data_ptr(), comp_size
             root, leaves = self.digest_device_blob_with_leaves(push_ptr, push_size,
                                                                chunk_size)

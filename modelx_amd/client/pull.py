@@ -106,6 +106,9 @@ class Puller:
         from ..wire import digest as dg
 
         dest = os.path.join(into_dir, desc.name)
+        # a byte-plane filter this client cannot undo is refused before
+        # anything is fetched or written
+        planes = types.parse_byte_planes(desc.annotations.get(types.ANNOTATION_BYTE_PLANES))
         raw_digest = desc.annotations.get(types.ANNOTATION_RAW_DIGEST, "")
         if os.path.isfile(dest) and raw_digest and _verify_digest_of_file(dest, raw_digest):
             if bar:
@@ -118,6 +121,9 @@ class Puller:
             self.pull_blob(repository, desc, comp_path, bar, plan_blobs=plan_blobs)
         with open(comp_path, "rb") as f:
             raw = _core.zstd_decompress_cpu(f.read())
+        if planes:
+            # stored planar: merge back, then verify the original bytes
+            raw = _core.byte_planes_cpu(raw, planes[0], planes[1], True)
         if raw_digest and not dg.verify_bytes(raw, raw_digest):
             raise ValueError(f"uncompressed digest mismatch for {desc.name}")
         tmp = dest + ".part"

@@ -17,6 +17,7 @@ from datetime import datetime, timezone
 from typing import List, Optional
 
 from ..wire import digest as dg
+from ..wire import errors as er
 from ..wire import types
 from . import extension as ext
 from .progress import Bar, MultiBar
@@ -51,17 +52,43 @@ def _file_descriptor(path: str, name: str, chunk_size: int, digest_mode: str) ->
     return desc
 
 
+def check_planes(planes, compress: str) -> None:
+    """``planes`` is 0 or an element size the byte-plane filter supports, and
+    only goes with ``compress="zstd"``."""
+    if isinstance(planes, bool) or planes not in (0,) + types.BYTE_PLANES_ELEMS:
+        raise er.ModelxError(er.ErrCode.UNSUPPORTED,
+                             f"planes must be 0, 2, 4 or 8, not {planes!r}")
+    if planes and compress != "zstd":
+        raise er.ModelxError(er.ErrCode.UNSUPPORTED,
+                             'planes needs compress="zstd": the byte-plane filter '
+                             "exists only inside +zstd blobs")
+
+
 def _zstd_file_descriptor(path: str, name: str, chunk_size: int,
-                          digest_mode: str, cache_dir: str) -> types.Descriptor:
+                          digest_mode: str, cache_dir: str,
+                          planes: int = 0) -> types.Descriptor:
     """Compress a file into the seekable multi-frame zstd format (CPU path
     of core/hip/zstd.hip's codec) and describe the COMPRESSED blob; the
-    uncompressed identity travels in raw-digest/raw-size annotations."""
+    uncompressed identity travels in raw-digest/raw-size annotations.
+
+    ``planes`` = 2, 4 or 8 stores the file's byte planes for that element
+    size instead (one plane per 128 KiB frame, literals-only encode) and
+    says so in the byte-planes annotation; the raw digest and size still
+    describe the file as it is. Meant for dense float weights: a mostly-zero
+    file compresses worse without the LZ stage."""
     from modelx_amd import _core
 
     st = os.stat(path)
     with open(path, "rb") as f:
         raw = f.read()
-    blob = _core.zstd_compress_cpu(raw, 128 << 10)
+    extra = {}
+    if planes:
+        group = planes * types.BYTE_PLANES_FRAME
+        blob = _core.zstd_compress_cpu(_core.byte_planes_cpu(raw, planes, group, False),
+                                       types.BYTE_PLANES_FRAME, literals_only=True)
+        extra[types.ANNOTATION_BYTE_PLANES] = types.format_byte_planes(planes, group)
+    else:
+        blob = _core.zstd_compress_cpu(raw, 128 << 10)
     comp_path = os.path.join(cache_dir, name + ".zst")
     with open(comp_path, "wb") as f:
         f.write(blob)
@@ -80,6 +107,7 @@ def _zstd_file_descriptor(path: str, name: str, chunk_size: int,
             types.ANNOTATION_CHUNK_SIZE: str(chunk_size),
             types.ANNOTATION_RAW_DIGEST: raw_chunked,
             types.ANNOTATION_RAW_SIZE: str(len(raw)),
+            **extra,
         },
     )
 
@@ -87,10 +115,13 @@ def _zstd_file_descriptor(path: str, name: str, chunk_size: int,
 def parse_manifest(basedir: str, configfile: str = "modelx.yaml",
                    chunk_size: int = dg.DEFAULT_CHUNK_SIZE,
                    digest_mode: str = "sha256",
-                   dir_format: str = "tar+gz", compress: str = "") -> types.Manifest:
+                   dir_format: str = "tar+gz", compress: str = "",
+                   planes: int = 0) -> types.Manifest:
     """Scan basedir into a Manifest (reference: push.go:67-100).
     Dot-files skipped; directories become tar.gz descriptors.
-    compress="zstd" stores file blobs in the seekable +zstd format."""
+    compress="zstd" stores file blobs in the seekable +zstd format;
+    planes=2/4/8 with it stores their byte planes (_zstd_file_descriptor)."""
+    check_planes(planes, compress)
     manifest = types.Manifest(media_type=types.MEDIA_TYPE_MODEL_MANIFEST_JSON)
     cache_dir = os.path.join(basedir, MODELX_CACHE_DIR)
     os.makedirs(cache_dir, exist_ok=True)
@@ -127,7 +158,8 @@ def parse_manifest(basedir: str, configfile: str = "modelx.yaml",
             manifest.blobs.append(desc)
         elif compress == "zstd":
             manifest.blobs.append(
-                _zstd_file_descriptor(path, entry, chunk_size, digest_mode, cache_dir))
+                _zstd_file_descriptor(path, entry, chunk_size, digest_mode, cache_dir,
+                                      planes))
         else:
             manifest.blobs.append(_file_descriptor(path, entry, chunk_size, digest_mode))
     manifest.blobs = types.sort_descriptors_by_name(manifest.blobs)  # push.go:98
@@ -144,9 +176,10 @@ class Pusher:
     def push(self, repository: str, version: str, basedir: str,
              configfile: str = "modelx.yaml", digest_mode: str = "sha256",
              chunk_size: int = dg.DEFAULT_CHUNK_SIZE, quiet: Optional[bool] = None,
-             dir_format: str = "tar+gz", compress: str = "") -> types.Manifest:
+             dir_format: str = "tar+gz", compress: str = "",
+             planes: int = 0) -> types.Manifest:
         manifest = parse_manifest(basedir, configfile, chunk_size, digest_mode, dir_format,
-                                  compress)
+                                  compress, planes)
         with MultiBar(f"push {repository}@{version}", self.concurrency, quiet=quiet) as mb:
             descs: List[types.Descriptor] = [manifest.config] + list(manifest.blobs)
             for desc in descs:

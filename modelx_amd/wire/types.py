@@ -57,6 +57,48 @@ MEDIA_TYPE_MODEL_FILE_ZSTD = "application/vnd.modelx.amd.file.v1+zstd"
 ANNOTATION_RAW_DIGEST = "modelx.amd/raw-digest"
 #   uncompressed size, bytes (decimal string)
 ANNOTATION_RAW_SIZE = "modelx.amd/raw-size"
+#   byte-plane filter of a +zstd blob, "<E>:<G>" in decimal: the compressed
+#   stream holds the raw bytes with each byte position of the E-byte element
+#   stored as its own plane, per group of G raw bytes
+#   (core/include/modelx/byteplane_host.hpp). E is 2, 4 or 8; G is a positive
+#   multiple of E (pushers use E * 128 KiB, one plane per zstd frame; readers
+#   take G from here). The media type stays ...file.v1+zstd and raw-digest /
+#   raw-size keep describing the original interleaved bytes, so a client that
+#   predates the annotation fails its raw-digest check instead of returning
+#   planar bytes.
+ANNOTATION_BYTE_PLANES = "modelx.amd/byte-planes"
+BYTE_PLANES_ELEMS = (2, 4, 8)
+BYTE_PLANES_FRAME = 128 << 10  # pushers' G is E * this: the zstd frame size
+
+
+def format_byte_planes(elem: int, group: int) -> str:
+    return f"{elem}:{group}"
+
+
+def parse_byte_planes(note) -> Optional[tuple]:
+    """``(E, G)`` from a byte-planes annotation value, ``None`` when the
+    annotation is absent (``""`` or ``None``). Anything else that is not
+    ``"<E>:<G>"`` with ASCII-decimal fields, E in {2, 4, 8}, G > 0 and
+    G % E == 0 raises ``ModelxError(UNSUPPORTED)``: a filter this client
+    cannot undo exactly must never be guessed at or skipped."""
+    from . import errors as er
+
+    if note is None or (isinstance(note, str) and note == ""):
+        return None
+
+    def bad():
+        return er.ModelxError(er.ErrCode.UNSUPPORTED,
+                              f"unsupported {ANNOTATION_BYTE_PLANES} annotation {note!r}")
+
+    if not isinstance(note, str):
+        raise bad()
+    fields = note.split(":")
+    if len(fields) != 2 or not all(f.isascii() and f.isdigit() for f in fields):
+        raise bad()
+    elem, group = int(fields[0]), int(fields[1])
+    if elem not in BYTE_PLANES_ELEMS or group <= 0 or group % elem:
+        raise bad()
+    return elem, group
 
 GO_ZERO_TIME = "0001-01-01T00:00:00Z"
 

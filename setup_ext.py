@@ -20,6 +20,7 @@ SOURCES = [
     "core/hip/tar.hip",
     "core/hip/dedup.hip",
     "core/hip/zstd.hip",
+    "core/hip/byteplane.hip",
     "core/src/zstd_cpu.cpp",
     "core/src/http.cpp",
     "core/src/json.cpp",
