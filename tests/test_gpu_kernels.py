@@ -224,7 +224,9 @@ class TestEngineTransfers:
 
 class TestZstdKernels:
     """GPU zstd kernels (core/hip/zstd.hip) vs the CPU path of the SAME
-    shared codec core, plus the libzstd interop oracle."""
+    shared codec core; libzstd decodes what the compress kernel wrote. The
+    libzstd interop oracle for the decoder (frames libzstd wrote) is
+    test_gpu_zstd_interop.py."""
 
     def _payloads(self):
         import random
