@@ -22,6 +22,7 @@ from dataclasses import dataclass, field
 from typing import Callable, Dict, List, Optional, Sequence, Tuple
 
 from ..wire import types
+from .gpu_rules import payload_descriptors
 
 DEFAULT_PIPELINE_CHUNK = 256 << 20
 
@@ -102,11 +103,7 @@ def fanout_pull_broadcast(dist, gpu_client, repository: str, version: str,
     rank = dist.get_rank()
     manifest = gpu_client.remote.get_manifest(repository, version)
     out = {}
-    for desc in manifest.blobs:
-        if desc.size == 0:
-            continue
-        if skip_sidecars and desc.media_type == types.MEDIA_TYPE_MODEL_LEAVES:
-            continue
+    for desc in payload_descriptors(manifest, skip_sidecars):
         tensor = torch.empty(desc.size, dtype=torch.uint8, device=dev)
         fetch = None
         if rank == src_rank:
