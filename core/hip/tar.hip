@@ -20,51 +20,23 @@
 using modelx::abi::CopySeg;
 using modelx::abi::PackSeg;
 using modelx::abi::TarEntry;
+using modelx::abi::TarWalkResult;
 
 namespace {
 
-__device__ uint64_t parse_octal(const uint8_t* p, int n) {
-  uint64_t v = 0;
-  for (int i = 0; i < n; i++) {
-    uint8_t c = p[i];
-    if (c == ' ' || c == 0) {
-      if (v) break;
-      continue;
-    }
-    if (c < '0' || c > '7') break;
-    v = (v << 3) | (c - '0');
-  }
-  return v;
-}
+constexpr int kIndexThreads = 64;  // one wave; only its first lane works
 
-// Single-thread sequential header walk. entries/count sized by caller.
-__global__ void tar_index_kernel(const uint8_t* __restrict__ tar, uint64_t tar_len,
-                                 TarEntry* __restrict__ entries, uint32_t max_entries,
-                                 uint32_t* __restrict__ count, uint32_t* __restrict__ error) {
+// Single-thread sequential header walk: tarcore::walk, the same steps the
+// host model runs (modelx/tar_core.hpp). entries sized by the caller. The
+// launch bound gives the one wave the registers to hold a whole header, so
+// the checksum's loads are all in flight together.
+__global__ __launch_bounds__(kIndexThreads) void tar_index_kernel(
+    const uint8_t* __restrict__ tar, uint64_t tar_len, TarEntry* __restrict__ entries,
+    uint32_t max_entries, TarWalkResult* __restrict__ result) {
   if (blockIdx.x != 0 || threadIdx.x != 0) return;
-  uint64_t off = 0;
-  uint32_t n = 0;
-  *error = 0;
-  while (off + 512 <= tar_len) {
-    const uint8_t* hdr = tar + off;
-    // empty block = end of archive
-    bool empty = true;
-    for (int i = 0; i < 512 && empty; i++) empty = hdr[i] == 0;
-    if (empty) break;
-    uint64_t size = parse_octal(hdr + 124, 12);
-    uint32_t mode = static_cast<uint32_t>(parse_octal(hdr + 100, 8));
-    uint32_t typeflag = hdr[156];
-    if (n < max_entries) {
-      entries[n] = TarEntry{off, off + 512, size, typeflag, mode};
-      n++;
-    } else {
-      *error = 2;  // table overflow
-      break;
-    }
-    uint64_t padded = (size + 511) & ~511ull;
-    off += 512 + padded;
-  }
-  *count = n;
+  TarWalkResult res;
+  modelx::tarcore::walk(tar, tar_len, entries, max_entries, &res);
+  *result = res;
 }
 
 constexpr int kScatterThreads = 256;
@@ -237,11 +209,11 @@ __global__ __launch_bounds__(kPackThreads) void tar_pack_kernel(
 extern "C" {
 
 hipError_t modelx_tar_index(const void* tar, uint64_t tar_len, TarEntry* entries,
-                            uint32_t max_entries, uint32_t* count_dev, uint32_t* error_dev,
+                            uint32_t max_entries, TarWalkResult* result_dev,
                             hipStream_t stream) {
-  hipLaunchKernelGGL(tar_index_kernel, dim3(1), dim3(64), 0, stream,
+  hipLaunchKernelGGL(tar_index_kernel, dim3(1), dim3(kIndexThreads), 0, stream,
                      static_cast<const uint8_t*>(tar), tar_len,
-                     entries, max_entries, count_dev, error_dev);
+                     entries, max_entries, result_dev);
   return hipGetLastError();
 }
 

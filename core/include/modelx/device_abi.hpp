@@ -10,18 +10,16 @@
 
 #include <cstdint>
 
+#include "modelx/tar_core.hpp"
 #include "modelx/zstd_host.hpp"
 
 namespace modelx {
 namespace abi {
 
-struct TarEntry {
-  uint64_t header_off;   // offset of the 512 B header block
-  uint64_t payload_off;  // offset of file data
-  uint64_t size;         // file size in bytes
-  uint32_t typeflag;     // '0'/'\0' regular, '5' dir, 'L' GNU longname, ...
-  uint32_t mode;         // octal-decoded
-};
+// One indexed header and the outcome of a header walk: tar_core.hpp's, which
+// the index kernel and the host model share.
+using TarEntry = tarcore::Entry;
+using TarWalkResult = tarcore::WalkResult;
 
 // Scatter segment: copies src[src_off..src_off+len) -> dst_ptr.
 struct CopySeg {
@@ -64,8 +62,11 @@ hipError_t modelx_sha256_chunk_leaves_many(const modelx::abi::ChunkLeavesDesc* d
                                            hipStream_t stream);
 hipError_t modelx_sha256_multibuf(const void* const* buffers, const uint64_t* lengths,
                                   uint32_t nbuf, void* digests, hipStream_t stream);
+// Walks the headers of the archive at `tar` (tarcore::walk): up to
+// max_entries entries and the count, error code and error offset in
+// *result_dev. Reads no byte at or past tar + tar_len.
 hipError_t modelx_tar_index(const void* tar, uint64_t tar_len, modelx::abi::TarEntry* entries,
-                            uint32_t max_entries, uint32_t* count_dev, uint32_t* error_dev,
+                            uint32_t max_entries, modelx::abi::TarWalkResult* result_dev,
                             hipStream_t stream);
 hipError_t modelx_tar_scatter(const void* tar, const modelx::abi::CopySeg* segs, uint32_t nsegs,
                               hipStream_t stream);

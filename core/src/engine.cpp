@@ -55,6 +55,7 @@ using modelx::abi::CopySeg;
 using modelx::abi::kDedupMaxProbes;
 using modelx::abi::PackSeg;
 using modelx::abi::TarEntry;
+using modelx::abi::TarWalkResult;
 using zstdhost::SeekEntry;
 
 // MODELX_ZSTD_FLAGS: bit0 disables the lane-parallel huffman encoder,
@@ -108,6 +109,20 @@ uint32_t checked_leaf_count(const char* who, size_t leaves_bytes, uint64_t chunk
                              std::to_string(chunk_size) + " (expected " +
                              std::to_string(want) + ")");
   return static_cast<uint32_t>(want);
+}
+
+// What tar_index returns, from the engine and from the host model alike.
+py::list indexed_files_to_py(const std::vector<tarhost::IndexedFile>& files) {
+  py::list out;
+  for (const tarhost::IndexedFile& f : files) {
+    py::dict e;
+    e["name"] = f.name;
+    e["offset"] = f.offset;
+    e["size"] = f.size;
+    e["mode"] = f.mode;
+    out.append(std::move(e));
+  }
+  return out;
 }
 
 struct Slot {
@@ -587,106 +602,71 @@ class GpuEngine {
 
   // ---------------------------------------------------- tar (directories) --
 
-  // Index a tar archive resident in HBM. Returns a list of
-  // (name, payload_off, size, mode) for regular files (GNU longnames
-  // resolved). Runs the sequential header walk on-device, gathers the header
-  // blocks with the scatter kernel, and reads names from one D2H copy.
+  // Index a tar archive resident in HBM: [{name, offset, size, mode}] for
+  // its regular files, as tarfile lists them. The header walk runs on the
+  // device (tar_core.hpp's, the one _core.tar_index_host runs on host
+  // bytes), the scatter kernel gathers the header blocks for one D2H copy,
+  // and tar_host.hpp checks the table against tar_len and resolves the
+  // names. A damaged or unsupported archive is a RuntimeError naming the
+  // cause and the header offset; no payload byte is read before the whole
+  // table has passed the host-side check.
   py::list tar_index(uintptr_t tar_ptr, uint64_t tar_len) {
     HIP_CHECK(hipSetDevice(device_));
     uint32_t max_entries = tarhost::kMaxIndexEntries;  // tar_pack emits no more
     std::vector<TarEntry> entries;
-    uint32_t count = 0, error = 0;
+    std::string headers;
     {
       py::gil_scoped_release release;
       DeviceBuffer dentries(max_entries * sizeof(TarEntry));
-      DeviceBuffer dcount_buf(2 * sizeof(uint32_t));
-      uint32_t* dcount = dcount_buf.get<uint32_t>();
+      DeviceBuffer dresult(sizeof(TarWalkResult));
       HIP_CHECK(modelx_tar_index(reinterpret_cast<void*>(tar_ptr), tar_len,
-                                 dentries.get<TarEntry>(), max_entries, dcount, dcount + 1,
-                                 hash_stream_));
+                                 dentries.get<TarEntry>(), max_entries,
+                                 dresult.get<TarWalkResult>(), hash_stream_));
       HIP_CHECK(hipStreamSynchronize(hash_stream_));
-      HIP_CHECK(hipMemcpy(&count, dcount, sizeof count, hipMemcpyDeviceToHost));
-      HIP_CHECK(hipMemcpy(&error, dcount + 1, sizeof error, hipMemcpyDeviceToHost));
-      if (error) throw std::runtime_error("tar_index: malformed archive or too many entries");
-      entries.resize(count);
-      if (count)
-        HIP_CHECK(hipMemcpy(entries.data(), dentries.get(), count * sizeof(TarEntry),
+      TarWalkResult res;
+      HIP_CHECK(hipMemcpy(&res, dresult.get(), sizeof res, hipMemcpyDeviceToHost));
+      if (res.error) throw tarhost::IndexError(res.error, res.error_off);
+      if (res.count > max_entries)
+        throw tarhost::IndexError(tarcore::kErrTooManyEntries, 0);
+      entries.resize(res.count);
+      if (res.count)
+        HIP_CHECK(hipMemcpy(entries.data(), dentries.get(), res.count * sizeof(TarEntry),
                             hipMemcpyDeviceToHost));
-    }
-    // gather headers (+ longname payloads) to host in one shot
-    std::string headers(static_cast<size_t>(count) * 512, '\0');
-    if (count) {
-      py::gil_scoped_release release;
-      DeviceBuffer dgather(headers.size());
-      std::vector<CopySeg> segs(count);
-      for (uint32_t i = 0; i < count; i++)
-        segs[i] = {entries[i].header_off, reinterpret_cast<uint64_t>(dgather.get()) + i * 512,
-                   512};
-      DeviceBuffer dsegs(segs.size() * sizeof(CopySeg));
-      HIP_CHECK(hipMemcpyAsync(dsegs.get(), segs.data(), segs.size() * sizeof(CopySeg),
-                               hipMemcpyHostToDevice, hash_stream_));
-      HIP_CHECK(modelx_tar_scatter(reinterpret_cast<void*>(tar_ptr), dsegs.get<CopySeg>(),
-                                   count, hash_stream_));
-      HIP_CHECK(hipStreamSynchronize(hash_stream_));
-      HIP_CHECK(hipMemcpy(&headers[0], dgather.get(), headers.size(), hipMemcpyDeviceToHost));
-    }
-    py::list out;
-    std::string pending_longname;
-    auto read_payload = [&](uint32_t i) {
-      std::string pl(static_cast<size_t>(entries[i].size), '\0');
-      if (!pl.empty()) {
-        py::gil_scoped_release release;
-        HIP_CHECK(hipMemcpy(&pl[0], reinterpret_cast<char*>(tar_ptr) + entries[i].payload_off,
-                            pl.size(), hipMemcpyDeviceToHost));
+      // before the gather below reads a header by these offsets
+      tarhost::validate_entries(entries, tar_len);
+      // gather the header blocks to the host in one shot
+      headers.assign(entries.size() * tarhost::kBlock, '\0');
+      if (!entries.empty()) {
+        DeviceBuffer dgather(headers.size());
+        std::vector<CopySeg> segs(entries.size());
+        for (size_t i = 0; i < entries.size(); i++)
+          segs[i] = {entries[i].header_off,
+                     reinterpret_cast<uint64_t>(dgather.get()) + i * tarhost::kBlock,
+                     tarhost::kBlock};
+        DeviceBuffer dsegs(segs.size() * sizeof(CopySeg));
+        HIP_CHECK(hipMemcpyAsync(dsegs.get(), segs.data(), segs.size() * sizeof(CopySeg),
+                                 hipMemcpyHostToDevice, hash_stream_));
+        HIP_CHECK(modelx_tar_scatter(reinterpret_cast<void*>(tar_ptr), dsegs.get<CopySeg>(),
+                                     static_cast<uint32_t>(segs.size()), hash_stream_));
+        HIP_CHECK(hipStreamSynchronize(hash_stream_));
+        HIP_CHECK(hipMemcpy(&headers[0], dgather.get(), headers.size(), hipMemcpyDeviceToHost));
       }
+    }
+    // payloads of 'L', 'x' and 'g' entries; resolve_names validates the
+    // table against tar_len before its first call
+    auto read_payload = [&](const TarEntry& e) {
+      std::string pl(static_cast<size_t>(e.size), '\0');
+      if (!pl.empty())
+        HIP_CHECK(hipMemcpy(&pl[0], reinterpret_cast<char*>(tar_ptr) + e.payload_off, pl.size(),
+                            hipMemcpyDeviceToHost));
       return pl;
     };
-    for (uint32_t i = 0; i < count; i++) {
-      const char* hdr = headers.data() + static_cast<size_t>(i) * 512;
-      uint32_t tf = entries[i].typeflag;
-      if (tf == 'L') {
-        // GNU longname: payload holds the next entry's name
-        std::string ln = read_payload(i);
-        while (!ln.empty() && ln.back() == '\0') ln.pop_back();
-        pending_longname = ln;
-        continue;
-      }
-      if (tf == 'x' || tf == 'X') {
-        // PAX extended header: "<len> key=value\n" records; path overrides
-        // the next entry's name (what Python tarfile emits for long names)
-        std::string px = read_payload(i);
-        size_t pos = 0;
-        while (pos < px.size()) {
-          size_t sp = px.find(' ', pos);
-          if (sp == std::string::npos) break;
-          long rec_len = atol(px.c_str() + pos);
-          if (rec_len <= 0 || pos + static_cast<size_t>(rec_len) > px.size()) break;
-          std::string rec = px.substr(sp + 1, pos + rec_len - sp - 2);  // drop trailing \n
-          if (rec.rfind("path=", 0) == 0) pending_longname = rec.substr(5);
-          pos += static_cast<size_t>(rec_len);
-        }
-        continue;
-      }
-      if (tf == 'g') continue;  // pax global header
-      std::string name;
-      if (!pending_longname.empty()) {
-        name = pending_longname;
-        pending_longname.clear();
-      } else {
-        name.assign(hdr, strnlen(hdr, 100));
-        // ustar prefix field (bytes 345..500)
-        std::string prefix(hdr + 345, strnlen(hdr + 345, 155));
-        if (!prefix.empty()) name = prefix + "/" + name;
-      }
-      if (tf != '0' && tf != 0) continue;  // regular files only
-      py::dict e;
-      e["name"] = name;
-      e["offset"] = entries[i].payload_off;
-      e["size"] = entries[i].size;
-      e["mode"] = entries[i].mode;
-      out.append(std::move(e));
+    std::vector<tarhost::IndexedFile> files;
+    {
+      py::gil_scoped_release release;
+      files = tarhost::resolve_names(entries, headers.data(), read_payload, tar_len);
     }
-    return out;
+    return indexed_files_to_py(files);
   }
 
   // Scatter payload segments: [(src_off, dst_dev_ptr, len), ...]
@@ -703,6 +683,7 @@ class GpuEngine {
       for (uint64_t off = 0; off < len; off += kPiece)
         pieces.push_back({src_off + off, dst + off, std::min(kPiece, len - off)});
     }
+    if (pieces.empty()) return;  // zero-length segments only
     DeviceBuffer dsegs(pieces.size() * sizeof(CopySeg));
     HIP_CHECK(hipMemcpyAsync(dsegs.get(), pieces.data(), pieces.size() * sizeof(CopySeg),
                              hipMemcpyHostToDevice, hash_stream_));
@@ -1417,6 +1398,21 @@ PYBIND11_MODULE(_core, m) {
         return out;
       },
       py::arg("members"));
+  // GpuEngine::tar_index on host bytes (tar_host.hpp): the same header walk
+  // and name resolution, the same result and the same RuntimeErrors. No GPU
+  // needed; the model the engine's index is tested against.
+  m.def(
+      "tar_index_host",
+      [](py::bytes data) {
+        std::string s = data;
+        std::vector<tarhost::IndexedFile> files;
+        {
+          py::gil_scoped_release release;
+          files = tarhost::index_host(reinterpret_cast<const uint8_t*>(s.data()), s.size());
+        }
+        return indexed_files_to_py(files);
+      },
+      py::arg("data"));
   m.def("zstd_compress_bound", &GpuEngine::zstd_compress_bound, py::arg("size"),
         py::arg("frame_raw") = (uint32_t)(128 << 10));
   // CPU codec path (same header-only core as the kernels) — used by the
