@@ -10,6 +10,7 @@
 
 #include <cstdint>
 
+#include "modelx/crc32c_core.hpp"
 #include "modelx/tar_core.hpp"
 #include "modelx/zstd_host.hpp"
 
@@ -49,6 +50,19 @@ struct ChunkLeavesDesc {
 // Linear-probe window of the chunk-dedup table (core/hip/dedup.hip): the
 // smallest table capacity the engine accepts.
 constexpr uint32_t kDedupMaxProbes = 64;
+
+// One range of modelx_crc32c_ranges (core/hip/crc32c.hip): `len` bytes at the
+// device address `ptr`. The kernel cuts the range's 16 B aligned body into
+// segments of kCrc32cSegmentBytes (crc32c::segment_count of them); seg_base
+// is the number of segments of all preceding ranges.
+struct CrcRange {
+  uint64_t ptr;
+  uint64_t len;
+  uint32_t seg_base;
+  uint32_t pad_;
+};
+
+constexpr uint64_t kCrc32cSegmentBytes = crc32c::kSegmentBytes;
 
 }  // namespace abi
 }  // namespace modelx
@@ -99,5 +113,11 @@ hipError_t modelx_dedup_gather(const uint64_t* src_addr_dev, const uint64_t* src
 // multiple of it.
 hipError_t modelx_byte_planes(const void* src, void* dst, uint64_t size, uint32_t elem,
                               uint64_t group, int merge, hipStream_t stream);
+// CRC-32C of `nranges` device ranges, out_dev[i] for ranges_dev[i]. Ranges may
+// be empty or overlap. seg_vals_dev is scratch of total_segments values, the
+// sum of the ranges' segment counts. Reads no byte outside a range.
+hipError_t modelx_crc32c_ranges(const modelx::abi::CrcRange* ranges_dev, uint32_t nranges,
+                                uint32_t total_segments, uint32_t* seg_vals_dev,
+                                uint32_t* out_dev, hipStream_t stream);
 
 }  // extern "C"

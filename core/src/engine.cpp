@@ -42,6 +42,7 @@
 #include <vector>
 
 #include "modelx/byteplane_host.hpp"
+#include "modelx/crc32c_core.hpp"
 #include "modelx/device_abi.hpp"
 #include "modelx/http.hpp"
 #include "modelx/tar_host.hpp"
@@ -52,6 +53,7 @@ namespace py = pybind11;
 using namespace modelx;
 using modelx::abi::ChunkLeavesDesc;
 using modelx::abi::CopySeg;
+using modelx::abi::CrcRange;
 using modelx::abi::kDedupMaxProbes;
 using modelx::abi::PackSeg;
 using modelx::abi::TarEntry;
@@ -742,6 +744,48 @@ class GpuEngine {
     return lay.total;
   }
 
+  // ----------------------------------------------------------- crc32c ----
+
+  // CRC-32C of many device ranges [(ptr, size)] in ONE launch pair on
+  // hash_stream_ (core/hip/crc32c.hip; the arithmetic is crc32c_core.hpp's):
+  // one descriptor upload, one sync, one D2H of 4 bytes per range. Ranges may
+  // be empty or overlap. Every range is checked before anything is launched.
+  std::vector<uint32_t> crc32c_ranges(
+      const std::vector<std::pair<uintptr_t, uint64_t>>& ranges) {
+    size_t n = ranges.size();
+    std::vector<uint32_t> out(n, 0);
+    if (!n) return out;
+    if (n > UINT32_MAX) throw std::runtime_error("crc32c_ranges: too many ranges");
+    std::vector<CrcRange> descs(n);
+    uint64_t total_segments = 0;
+    for (size_t i = 0; i < n; i++) {
+      auto [ptr, size] = ranges[i];
+      if (size && (ptr == 0 || ptr > UINTPTR_MAX - size))
+        throw std::runtime_error("crc32c_ranges: range " + std::to_string(i) +
+                                 " is null or wraps the address space");
+      descs[i] = {ptr, size, static_cast<uint32_t>(total_segments), 0};
+      total_segments += crc32c::segment_count(ptr, size);
+      // seg_base is 32-bit: 2^32 segments are 512 TiB
+      if (total_segments > UINT32_MAX)
+        throw std::runtime_error("crc32c_ranges: ranges too large for one call");
+    }
+    HIP_CHECK(hipSetDevice(device_));
+    py::gil_scoped_release release;
+    std::lock_guard<std::mutex> lk(crc_mu_);
+    CrcRange* ddescs = cs_descs_.reserve<CrcRange>(n * sizeof(CrcRange));
+    uint32_t* dsegs =
+        cs_segs_.reserve<uint32_t>(std::max<uint64_t>(total_segments, 1) * sizeof(uint32_t));
+    uint32_t* dout = cs_out_.reserve<uint32_t>(n * sizeof(uint32_t));
+    HIP_CHECK(hipMemcpyAsync(ddescs, descs.data(), n * sizeof(CrcRange), hipMemcpyHostToDevice,
+                             hash_stream_));
+    HIP_CHECK(modelx_crc32c_ranges(ddescs, static_cast<uint32_t>(n),
+                                   static_cast<uint32_t>(total_segments), dsegs, dout,
+                                   hash_stream_));
+    HIP_CHECK(hipStreamSynchronize(hash_stream_));
+    HIP_CHECK(hipMemcpy(out.data(), dout, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    return out;
+  }
+
   // ------------------------------------------------------ byte planes ----
 
   // Byte-plane split (merge=false) or merge (merge=true) of device buffers
@@ -1307,6 +1351,8 @@ class GpuEngine {
   uint64_t dedup_cap_ = 0;
   DeviceBuffer dedup_dropped_;  // one uint32_t
   DeviceScratch ds_leaves_, ds_addr_, ds_len_;
+  std::mutex crc_mu_;  // guards the crc32c_ranges scratch below
+  DeviceScratch cs_descs_, cs_segs_, cs_out_;
 };
 
 bool hip_available() {
@@ -1371,6 +1417,7 @@ PYBIND11_MODULE(_core, m) {
            py::arg("size"), py::arg("frame_raw"), py::arg("dst_ptr"), py::arg("dst_cap"),
            py::arg("literals_only") = false)
       .def("byte_planes", &GpuEngine::byte_planes, py::arg("items"), py::arg("merge"))
+      .def("crc32c_ranges", &GpuEngine::crc32c_ranges, py::arg("ranges"))
       .def("zstd_decompress_device", &GpuEngine::zstd_decompress_device, py::arg("src_ptr"),
            py::arg("src_len"), py::arg("dst_ptr"), py::arg("dst_cap"))
       .def("synchronize", &GpuEngine::synchronize);
@@ -1451,6 +1498,25 @@ PYBIND11_MODULE(_core, m) {
         return py::bytes(out);
       },
       py::arg("data"), py::arg("elem"), py::arg("group"), py::arg("merge") = false);
+  // CRC-32C of host bytes (crc32c_core.hpp): the SSE4.2 instruction where the
+  // CPU has it, or with model=True the bytewise table loop that is the host
+  // model of the kernel. crc32c_mul_xn advances a register through nbytes
+  // zero bytes; crc32c_combine gives crc(A || B) from crc(A), crc(B), len(B).
+  m.def(
+      "crc32c_host",
+      [](py::bytes data, bool model) {
+        std::string_view s = data;
+        py::gil_scoped_release release;
+        return crc32c::crc(s.data(), s.size(), model);
+      },
+      py::arg("data"), py::arg("model") = false);
+  m.def(
+      "crc32c_mul_xn",
+      [](uint32_t crc, uint64_t nbytes) { return crc32c::mul_xn(crc, nbytes); },
+      py::arg("crc"), py::arg("nbytes"));
+  m.def("crc32c_combine", &crc32c::combine, py::arg("crc_a"), py::arg("crc_b"),
+        py::arg("len_b"));
+  m.attr("CRC32C_SEGMENT_BYTES") = modelx::abi::kCrc32cSegmentBytes;
   // One-shot GET through the NATIVE http client (the exact code path the
   // engine's ranged fetches use, incl. TLS) — lets the GPU-less suite prove
   // https presigned-URL support against a TLS server.

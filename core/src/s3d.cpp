@@ -25,6 +25,7 @@
 #include <ctime>
 #include <string>
 
+#include "modelx/crc32c_core.hpp"
 #include "modelx/http.hpp"
 #include "modelx/sha256.hpp"
 #include "modelx/sigv4.hpp"
@@ -81,7 +82,39 @@ std::string obj_path(const std::string& bucket, const std::string& key) {
 
 std::string mpu_dir(const std::string& upload_id) { return g_cfg.root + "/.mpu/" + upload_id; }
 
-bool write_stream_to(const std::string& path, http::Request& req, std::string* etag) {
+// x-amz-checksum-crc32c: standard base64 of the checksum's four bytes, most
+// significant first. False unless `v` is exactly that.
+bool parse_crc32c_header(const std::string& v, uint32_t* out) {
+  static const char kAlphabet[] =
+      "ABCDEFGHIJKLMNOPQRSTUVWXYZabcdefghijklmnopqrstuvwxyz0123456789+/";
+  if (v.size() != 8 || v[6] != '=' || v[7] != '=') return false;
+  uint64_t bits = 0;
+  for (int i = 0; i < 6; i++) {
+    const char* at = v[i] ? strchr(kAlphabet, v[i]) : nullptr;
+    if (!at) return false;
+    bits = (bits << 6) | static_cast<uint64_t>(at - kAlphabet);
+  }
+  if (bits & 0xF) return false;  // 36 bits carry 32: the pad bits are zero
+  *out = static_cast<uint32_t>(bits >> 4);
+  return true;
+}
+
+std::string format_crc32c_header(uint32_t crc) {
+  static const char kAlphabet[] =
+      "ABCDEFGHIJKLMNOPQRSTUVWXYZabcdefghijklmnopqrstuvwxyz0123456789+/";
+  uint64_t bits = static_cast<uint64_t>(crc) << 4;
+  std::string v(8, '=');
+  for (int i = 0; i < 6; i++) v[i] = kAlphabet[(bits >> (30 - 6 * i)) & 63];
+  return v;
+}
+
+// Stores the request body at `path` through a temporary file. With
+// `expect_crc32c` the body goes through user space (no splice), is
+// checksummed as it is written, and is renamed into place only if its
+// CRC-32C is *expect_crc32c; a mismatch removes the temporary file, sets
+// *bad_digest and returns false.
+bool write_stream_to(const std::string& path, http::Request& req, std::string* etag,
+                     const uint32_t* expect_crc32c = nullptr, bool* bad_digest = nullptr) {
   if (!mkdirs_for(path)) return false;
   std::string tmp = path + ".tmp" + std::to_string(getpid());
   int fd = ::open(tmp.c_str(), O_RDWR | O_CREAT | O_TRUNC | O_CLOEXEC, 0644);
@@ -98,7 +131,7 @@ bool write_stream_to(const std::string& path, http::Request& req, std::string* e
     const char* v = getenv("MODELX_S3D_SPLICE");
     return !(v && *v == '0');
   }();
-  if (use_splice && req.content_length > 0) {
+  if (use_splice && req.content_length > 0 && !expect_crc32c) {
     // drain any bytes the header parser buffered first
     char small[16384];
     while (req.body_remaining > 0 && req.raw_fd_if_plain() < 0) {
@@ -161,6 +194,7 @@ bool write_stream_to(const std::string& path, http::Request& req, std::string* e
     return true;
   }
   std::vector<char> buf(4 << 20);
+  uint32_t crc = crc32c::kInit;
   while (true) {
     ssize_t r = req.read_body(buf.data(), buf.size());
     if (r < 0) {
@@ -169,6 +203,7 @@ bool write_stream_to(const std::string& path, http::Request& req, std::string* e
       return false;
     }
     if (r == 0) break;
+    if (expect_crc32c) crc = crc32c::update(crc, buf.data(), static_cast<size_t>(r));
     ssize_t off = 0;
     while (off < r) {
       ssize_t w = ::write(fd, buf.data() + off, static_cast<size_t>(r - off));
@@ -187,11 +222,49 @@ bool write_stream_to(const std::string& path, http::Request& req, std::string* e
     ::unlink(tmp.c_str());
     return false;
   }
+  if (expect_crc32c && (crc ^ crc32c::kInit) != *expect_crc32c) {
+    ::unlink(tmp.c_str());
+    if (bad_digest) *bad_digest = true;
+    return false;
+  }
   if (::rename(tmp.c_str(), path.c_str()) != 0) {
     ::unlink(tmp.c_str());
     return false;
   }
   if (etag) *etag = "\"s3d-" + std::to_string(total) + "\"";
+  return true;
+}
+
+// The body of a PUT object or UploadPart into `path`, verified against the
+// request's x-amz-checksum-crc32c when it carries one. Returns true when the
+// bytes are in place; otherwise the error response has been written. A
+// request without the header takes write_stream_to's usual path, splice
+// included.
+bool store_put_body(const std::string& path, http::Request& req, http::ResponseWriter& w,
+                    std::string* etag) {
+  auto ck = req.headers.find("x-amz-checksum-crc32c");
+  uint32_t want = 0;
+  bool checked = ck != req.headers.end();
+  if (checked && !parse_crc32c_header(ck->second, &want)) {
+    // before any body byte is stored; the server loop drains the unread body
+    w.write_all(400,
+                "<Error><Code>InvalidRequest</Code><Message>Value for x-amz-checksum-crc32c "
+                "header is invalid.</Message></Error>",
+                "application/xml");
+    return false;
+  }
+  bool bad_digest = false;
+  if (!write_stream_to(path, req, etag, checked ? &want : nullptr, &bad_digest)) {
+    if (bad_digest)
+      w.write_all(400,
+                  "<Error><Code>BadDigest</Code><Message>The CRC32C you specified did not "
+                  "match the calculated checksum.</Message></Error>",
+                  "application/xml");
+    else
+      w.write_all(500, "<Error><Code>InternalError</Code></Error>", "application/xml");
+    return false;
+  }
+  if (checked) w.set_header("x-amz-checksum-crc32c", format_crc32c_header(want));
   return true;
 }
 
@@ -545,10 +618,7 @@ void handle(http::Request& req, http::ResponseWriter& w) {
     snprintf(name, sizeof name, "%06d", part);
     std::string ppath = mpu_dir(req.query["uploadId"]) + "/" + name;
     std::string etag;
-    if (!write_stream_to(ppath, req, &etag)) {
-      w.write_all(500, "<Error><Code>InternalError</Code></Error>", "application/xml");
-      return;
-    }
+    if (!store_put_body(ppath, req, w, &etag)) return;
     w.set_header("ETag", etag);
     w.write_all(200, "");
     return;
@@ -556,10 +626,7 @@ void handle(http::Request& req, http::ResponseWriter& w) {
 
   if (req.method == "PUT") {
     std::string etag;
-    if (!write_stream_to(path, req, &etag)) {
-      w.write_all(500, "<Error><Code>InternalError</Code></Error>", "application/xml");
-      return;
-    }
+    if (!store_put_body(path, req, w, &etag)) return;
     // content-type sidecar so HEAD/GET can return it
     auto ct = req.headers.find("Content-Type");
     if (ct != req.headers.end() && !ct->second.empty()) {

@@ -920,16 +920,20 @@ class GpuClient:
         self._stat("gpu-digest", size, t0)
         return root, leaves
 
-    def _upload_small(self, repository: str, desc: types.Descriptor, data: bytes) -> None:
+    def _upload_small(self, repository: str, desc: types.Descriptor, data: bytes,
+                      part_checksum: str = "") -> None:
         loc = self.remote.get_blob_location(repository, desc, "upload")
         if loc is None:
             return self.remote.upload_blob_content(repository, desc, data)
         import requests
 
         p = (loc.properties.get("parts") or [{}])[0]
+        headers = _signed_headers(p)
+        if part_checksum:
+            headers.update(rules.part_checksum_headers(_core().crc32c_host(data)))
         for attempt in range(self.PART_RETRIES):
             try:
-                requests.request(p.get("method") or "PUT", p["url"], headers=_signed_headers(p),
+                requests.request(p.get("method") or "PUT", p["url"], headers=headers,
                                  data=data, verify=_tls_verify()).raise_for_status()
                 return
             except Exception:
@@ -937,20 +941,28 @@ class GpuClient:
                     raise
 
     def _upload_small_once(self, repository: str, desc: types.Descriptor,
-                           data: bytes) -> types.Descriptor:
+                           data: bytes, part_checksum: str = "") -> types.Descriptor:
         """Upload a small host blob unless the registry already has it."""
         if not self.remote.head_blob(repository, desc.digest):
-            self._upload_small(repository, desc, data)
+            if part_checksum:
+                self._upload_small(repository, desc, data, part_checksum)
+            else:
+                self._upload_small(repository, desc, data)
         return desc
 
-    def _push_part_retrying(self, part: dict, ptr: int, length: int) -> None:
+    def _push_part_retrying(self, part: dict, ptr: int, length: int,
+                            extra_headers: Optional[Dict[str, str]] = None) -> None:
         """One presigned part from device memory, retried on transport
         failure with a fresh connection (the engine drops broken sockets
-        from its pool on error)."""
+        from its pool on error). ``extra_headers`` (the part checksum) go
+        with every attempt: each one is a fresh D2H of the same source, so a
+        store that refuses the body (HTTP 400, a RuntimeError like any other
+        status) is retried too."""
+        headers = {**_signed_headers(part), **(extra_headers or {})}
         for attempt in range(self.PART_RETRIES):
             try:
                 self.engine.push_part_from_device(part["url"], part.get("method") or "PUT",
-                                                  _signed_headers(part), ptr, length)
+                                                  headers, ptr, length)
                 return
             except RuntimeError:
                 if attempt == self.PART_RETRIES - 1:
@@ -958,9 +970,19 @@ class GpuClient:
 
     def push_blob_from_device(self, repository: str, desc: types.Descriptor, ptr: int,
                               part_bytes: int = DEFAULT_PART_BYTES,
-                              parallel: int = DEFAULT_PUSH_PARALLEL) -> None:
+                              parallel: int = DEFAULT_PUSH_PARALLEL,
+                              part_checksum: str = "") -> None:
         """Presigned (multi)part upload of device memory. HEAD-dedup first
-        (push.go:169-177 semantics)."""
+        (push.go:169-177 semantics).
+
+        ``part_checksum="crc32c"`` makes the object store verify every part:
+        the CRC-32C of each part is computed on the GPU from the source bytes
+        (one ``crc32c_ranges`` launch for all parts, before the first byte
+        enters the pinned ring) and sent as ``x-amz-checksum-crc32c``; a
+        store that checks it refuses a damaged body with HTTP 400, which the
+        part retry answers with a fresh D2H. The registry-stream fallback (no
+        presigned location) has no part requests and ignores the option."""
+        rules.check_part_checksum(part_checksum)
         self._sync_producers()
         t0 = time.monotonic()
         if self.remote.head_blob(repository, desc.digest):
@@ -978,8 +1000,15 @@ class GpuClient:
             self._stat("push-registry-stream", size, t0)
             return
         parts = loc.properties.get("parts") or []
-        _map(lambda job: self._push_part_retrying(job[0], ptr + job[1][0], job[1][1]),
-             zip(parts, rules.part_ranges(size, len(parts))), parallel)
+        ranges = rules.part_ranges(size, len(parts))
+        extra = [None] * len(parts)
+        if part_checksum and parts:
+            t1 = time.monotonic()
+            crcs = self.engine.crc32c_ranges([(ptr + off, ln) for off, ln in ranges])
+            extra = [rules.part_checksum_headers(c) for c in crcs]
+            self._stat("push-part-checksum", size, t1, parts=len(parts))
+        _map(lambda job: self._push_part_retrying(job[0], ptr + job[1][0], job[1][1], job[2]),
+             zip(parts, ranges, extra), parallel)
         self._stat("push-upload", size, t0, parts=len(parts))
 
     def _canonical_digests(self, blobs, phase: str) -> List[str]:
@@ -1058,7 +1087,8 @@ class GpuClient:
         return _PushBlob(name, ptr, size, media_type, main, root, leaves, notes, keep)
 
     def _upload_blob(self, repository: str, blob: _PushBlob, chunk_size: int,
-                     part_bytes: int, now) -> Tuple[types.Descriptor, types.Descriptor]:
+                     part_bytes: int, now,
+                     part_checksum: str = "") -> Tuple[types.Descriptor, types.Descriptor]:
         """Upload a digested blob and its leaves sidecar; returns both
         descriptors. The sidecar (32 B per chunk) enables chunk-level
         resume/refetch/dedup on pull; it is listed in the manifest so GC
@@ -1071,11 +1101,15 @@ class GpuClient:
                          types.ANNOTATION_CHUNK_SIZE: str(chunk_size),
                          types.ANNOTATION_LEAVES_BLOB: leaves_digest,
                          **blob.notes})
-        self.push_blob_from_device(repository, desc, blob.ptr, part_bytes=part_bytes)
+        if part_checksum:
+            self.push_blob_from_device(repository, desc, blob.ptr, part_bytes=part_bytes,
+                                       part_checksum=part_checksum)
+        else:
+            self.push_blob_from_device(repository, desc, blob.ptr, part_bytes=part_bytes)
         ldesc = types.Descriptor(
             name=blob.name + ".leaves", media_type=types.MEDIA_TYPE_MODEL_LEAVES,
             digest=leaves_digest, size=len(blob.leaves), modified=now)
-        return desc, self._upload_small_once(repository, ldesc, blob.leaves)
+        return desc, self._upload_small_once(repository, ldesc, blob.leaves, part_checksum)
 
     def push_from_gpu(self, repository: str, version: str,
                       tensors: Dict[str, "torch.Tensor"], config_yaml: str = "",
@@ -1083,7 +1117,7 @@ class GpuClient:
                       part_bytes: int = DEFAULT_PART_BYTES,
                       compress: str = "", digest_mode: str = "chunked",
                       dirs: Optional[Dict[str, Dict[str, "torch.Tensor"]]] = None,
-                      planes=0) -> types.Manifest:
+                      planes=0, part_checksum: str = "") -> types.Manifest:
         """Digest on GPU → presigned multipart upload → manifest PUT last.
         With ``compress="zstd"`` each tensor is compressed on-GPU into a
         seekable multi-frame zstd blob (core/hip/zstd.hip) first; the
@@ -1121,7 +1155,17 @@ class GpuClient:
         tensor. ``pull_dir_to_gpu`` and the CPU ``Client.pull`` both read it
         back. Every directory is packed (and so validated) before the first
         upload, so until the push returns HBM holds each directory twice: the
-        source tensors and their archive."""
+        source tensors and their archive.
+
+        ``part_checksum`` is ``""`` or ``"crc32c"``. With ``"crc32c"`` every
+        presigned upload of the push carries ``x-amz-checksum-crc32c``, so a
+        store that verifies it (modelx-s3d, MinIO, AWS) stores only the bytes
+        that were in HBM: device blobs get one value per part from the GPU
+        (core/hip/crc32c.hip, ``push_blob_from_device``), the config and the
+        leaves sidecars theirs from the host. Blobs that travel through the
+        registry (no presigned location) are not covered. The kernel's time
+        is the ``push-part-checksum`` phase of ``last_stats``."""
+        rules.check_part_checksum(part_checksum)
         if compress not in ("", "zstd"):
             raise er.ModelxError(er.ErrCode.UNSUPPORTED, f"unknown compression {compress!r}")
         if digest_mode not in ("chunked", "sha256"):
@@ -1152,10 +1196,11 @@ class GpuClient:
         cfg = config_yaml.encode() or b"description: pushed from GPU\n"
         manifest.config = self._upload_small_once(repository, types.Descriptor(
             name="modelx.yaml", media_type=types.MEDIA_TYPE_MODEL_CONFIG_YAML,
-            digest=dg.sha256_digest(cfg), size=len(cfg), modified=now), cfg)
+            digest=dg.sha256_digest(cfg), size=len(cfg), modified=now), cfg, part_checksum)
 
         def upload(blob: _PushBlob):
-            return self._upload_blob(repository, blob, chunk_size, part_bytes, now)
+            return self._upload_blob(repository, blob, chunk_size, part_bytes, now,
+                                     part_checksum)
 
         def push_one(name: str):
             # digest and upload per tensor, so that a compressed copy lives

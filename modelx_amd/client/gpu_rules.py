@@ -6,7 +6,8 @@ here, so a rule read in two places cannot drift apart.
 """
 from __future__ import annotations
 
-from typing import List, Optional, Tuple
+import base64
+from typing import Dict, List, Optional, Tuple
 
 from ..wire import digest as dg
 from ..wire import errors as er
@@ -156,6 +157,24 @@ def part_ranges(size: int, nparts: int) -> List[Tuple[int, int]]:
     base = size // nparts
     return [(i * base, base if i < nparts - 1 else size - i * base)
             for i in range(nparts)]
+
+
+PART_CHECKSUM_HEADER = "x-amz-checksum-crc32c"
+
+
+def check_part_checksum(part_checksum) -> None:
+    """The ``part_checksum`` option of a GPU push: ``""`` (none) or
+    ``"crc32c"``; anything else is UNSUPPORTED."""
+    if part_checksum not in ("", "crc32c"):
+        raise er.ModelxError(er.ErrCode.UNSUPPORTED,
+                             f"unknown part_checksum {part_checksum!r} "
+                             "(supported: '' and 'crc32c')")
+
+
+def part_checksum_headers(crc: int) -> Dict[str, str]:
+    """The upload header that carries a CRC-32C value: base64 of its four
+    bytes, most significant first, as S3 reads ``x-amz-checksum-crc32c``."""
+    return {PART_CHECKSUM_HEADER: base64.b64encode(crc.to_bytes(4, "big")).decode()}
 
 
 def check_dir_names(tensors, dirs) -> None:

@@ -21,10 +21,17 @@ SOURCES = [
     "core/hip/dedup.hip",
     "core/hip/zstd.hip",
     "core/hip/byteplane.hip",
+    "core/hip/crc32c.hip",
     "core/src/zstd_cpu.cpp",
     "core/src/http.cpp",
     "core/src/json.cpp",
 ]
+
+# crc32c.hip is integer work throughout: keep the compiler from forming packed
+# fp32 instructions in it.
+EXTRA_FLAGS = {
+    "core/hip/crc32c.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
+}
 
 
 def ext_path() -> str:
@@ -63,7 +70,8 @@ def build() -> str:
             if not newer_hdr:
                 objs.append(obj)
                 continue
-        cmd = [HIPCC, "-c", src_abs, "-o", obj] + common + (["-x", "hip"] if src.endswith(".hip") else [])
+        cmd = [HIPCC, "-c", src_abs, "-o", obj] + common + EXTRA_FLAGS.get(src, []) + (
+            ["-x", "hip"] if src.endswith(".hip") else [])
         print("+", " ".join(cmd), flush=True)
         subprocess.run(cmd, check=True)
         objs.append(obj)
