@@ -25,6 +25,7 @@
 
 #include <cstdint>
 
+#include "modelx/copy_shifted.hpp"
 #include "modelx/device_abi.hpp"
 
 namespace {
@@ -145,6 +146,90 @@ __global__ __launch_bounds__(kGatherThreads) void dedup_gather_kernel(
   }
 }
 
+// ---- chunks off the grid (content-defined chunking) ----
+// The same table and entry; a chunk is (address, length) instead of an index
+// on a grid. Grid and off-grid entries coexist: a probe hits only when digest
+// and length both match.
+
+using modelx::abi::DedupRange;
+
+// digests[i] digests the ranges[i].len bytes at ranges[i].at; the digests of
+// one launch are pairwise distinct (see the header comment).
+__global__ void dedup_insert_ranges_kernel(const u8* __restrict__ digests,
+                                           const DedupRange* __restrict__ ranges, u32 n,
+                                           DedupEntry* __restrict__ tab, u64 cap_mask,
+                                           u32* __restrict__ dropped) {
+  u32 i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const u8* d = digests + (u64)i * 32;
+  u64 key = load_key(d);
+  if (key == 0) return;  // sentinel collision: skip (dedup is best-effort)
+  DedupRange r = ranges[i];
+  u64 h = key & cap_mask;
+  for (u32 p = 0; p < kMaxProbes; p++) {
+    u64 slot = (h + p) & cap_mask;
+    u64 prev = atomicCAS(reinterpret_cast<unsigned long long*>(&tab[slot].key), 0ull,
+                         (unsigned long long)key);
+    if (prev == 0) {
+      tab[slot].addr = r.at;
+      tab[slot].len = r.len;
+      for (int k = 0; k < 3; k++) tab[slot].digest_hi[k] = load_key(d + 8 + 8 * k);
+      __threadfence();
+      return;
+    }
+    if (prev == key) {
+      bool same = true;
+      for (int k = 0; k < 3 && same; k++)
+        same = tab[slot].digest_hi[k] == load_key(d + 8 + 8 * k);
+      if (same) return;  // first wins
+    }
+  }
+  atomicAdd(dropped, 1);
+}
+
+__global__ void dedup_probe_ranges_kernel(const u8* __restrict__ digests,
+                                          const DedupRange* __restrict__ ranges, u32 n,
+                                          const DedupEntry* __restrict__ tab, u64 cap_mask,
+                                          u64* __restrict__ src_addr) {
+  u32 i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const u8* d = digests + (u64)i * 32;
+  u64 key = load_key(d);
+  u64 want = ranges[i].len;
+  src_addr[i] = 0;
+  if (key == 0 || want == 0) return;
+  u64 h = key & cap_mask;
+  for (u32 p = 0; p < kMaxProbes; p++) {
+    u64 slot = (h + p) & cap_mask;
+    u64 k = tab[slot].key;
+    if (k == 0) return;  // empty -> not present
+    if (k == key) {
+      bool same = tab[slot].len == want;
+      for (int q = 0; q < 3 && same; q++) same = tab[slot].digest_hi[q] == load_key(d + 8 + 8 * q);
+      if (same) {
+        src_addr[i] = tab[slot].addr;
+        return;
+      }
+    }
+  }
+}
+
+// One workgroup per chunk; skips misses. Off-grid chunks start at arbitrary
+// byte addresses on both sides, so differing 16 B phases are the common case:
+// the body stores full 16 B words on the destination's grid, built from two
+// adjacent aligned source words (modelx/copy_shifted.hpp).
+__global__ __launch_bounds__(modelx::devcopy::kPackThreads) void dedup_gather_ranges_kernel(
+    const u64* __restrict__ src_addr, const DedupRange* __restrict__ ranges, u32 n,
+    u64 dst_base) {
+  u32 c = blockIdx.x;
+  if (c >= n) return;
+  u64 sa = src_addr[c];
+  if (sa == 0) return;
+  DedupRange r = ranges[c];
+  modelx::devcopy::copy_to_aligned_grid(reinterpret_cast<const u8*>(sa),
+                                        reinterpret_cast<u8*>(dst_base + r.at), r.len);
+}
+
 }  // namespace
 
 extern "C" {
@@ -180,6 +265,34 @@ hipError_t modelx_dedup_gather(const uint64_t* src_addr_dev, const uint64_t* src
   if (nchunks == 0) return hipSuccess;
   hipLaunchKernelGGL(dedup_gather_kernel, dim3(nchunks), dim3(kGatherThreads), 0, stream,
                      src_addr_dev, src_len_dev, nchunks, dst_base, chunk_size);
+  return hipGetLastError();
+}
+
+hipError_t modelx_dedup_insert_ranges(const void* digests_dev, const DedupRange* ranges_dev,
+                                      uint32_t n, void* table, uint64_t cap,
+                                      uint32_t* dropped_dev, hipStream_t stream) {
+  if (n == 0) return hipSuccess;
+  hipLaunchKernelGGL(dedup_insert_ranges_kernel, dim3((n + 255) / 256), dim3(256), 0, stream,
+                     static_cast<const u8*>(digests_dev), ranges_dev, n,
+                     static_cast<DedupEntry*>(table), cap - 1, dropped_dev);
+  return hipGetLastError();
+}
+
+hipError_t modelx_dedup_probe_ranges(const void* digests_dev, const DedupRange* ranges_dev,
+                                     uint32_t n, const void* table, uint64_t cap,
+                                     uint64_t* src_addr_dev, hipStream_t stream) {
+  if (n == 0) return hipSuccess;
+  hipLaunchKernelGGL(dedup_probe_ranges_kernel, dim3((n + 255) / 256), dim3(256), 0, stream,
+                     static_cast<const u8*>(digests_dev), ranges_dev, n,
+                     static_cast<const DedupEntry*>(table), cap - 1, src_addr_dev);
+  return hipGetLastError();
+}
+
+hipError_t modelx_dedup_gather_ranges(const uint64_t* src_addr_dev, const DedupRange* ranges_dev,
+                                      uint32_t n, uint64_t dst_base, hipStream_t stream) {
+  if (n == 0) return hipSuccess;
+  hipLaunchKernelGGL(dedup_gather_ranges_kernel, dim3(n), dim3(modelx::devcopy::kPackThreads), 0,
+                     stream, src_addr_dev, ranges_dev, n, dst_base);
   return hipGetLastError();
 }
 

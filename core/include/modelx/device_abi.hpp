@@ -64,6 +64,36 @@ struct CrcRange {
 
 constexpr uint64_t kCrc32cSegmentBytes = crc32c::kSegmentBytes;
 
+// Candidate kernel (core/hip/cdc.hip). A workgroup owns kCdcTileBytes on the
+// 16 B grid of the range's first byte: tile k covers the addresses
+// [(ptr & ~15) + k * kCdcTileBytes, ... + kCdcTileBytes) that lie in the range.
+// 32 KiB keeps tile, halo, gear table and hit list under 40 KiB of LDS, four
+// workgroups to a CU (profiles/cdc_kernel.md).
+constexpr uint32_t kCdcTileBytes = 32u << 10;
+constexpr uint32_t kCdcMaxTileCap = 2048;  // hit-list entries a tile can keep
+constexpr uint32_t kCdcMaxBlocks = 256 * 8;
+
+inline uint64_t cdc_tile_phase(uint64_t ptr) { return ptr & 15u; }
+
+inline uint64_t cdc_tile_count(uint64_t ptr, uint64_t len) {
+  return len ? (cdc_tile_phase(ptr) + len + kCdcTileBytes - 1) / kCdcTileBytes : 0;
+}
+
+// Hit-list capacity per tile at `bits`: four times the expected count of
+// random data plus slack, so only periodic data or a tiny `bits` overflows.
+inline uint32_t cdc_tile_cap(uint32_t bits) {
+  uint64_t want = 32 + 4 * (static_cast<uint64_t>(kCdcTileBytes) >> bits);
+  return want < kCdcMaxTileCap ? static_cast<uint32_t>(want) : kCdcMaxTileCap;
+}
+
+// One chunk of the off-grid dedup kernels (core/hip/dedup.hip). insert: `at`
+// is the chunk's device address; probe: `at` is unused; gather: `at` is the
+// chunk's byte offset in the destination.
+struct DedupRange {
+  uint64_t at;
+  uint64_t len;
+};
+
 }  // namespace abi
 }  // namespace modelx
 
@@ -107,6 +137,30 @@ hipError_t modelx_dedup_probe(const void* leaves_dev, uint32_t nchunks, uint64_t
 hipError_t modelx_dedup_gather(const uint64_t* src_addr_dev, const uint64_t* src_len_dev,
                                uint32_t nchunks, uint64_t dst_base, uint64_t chunk_size,
                                hipStream_t stream);
+// The same table for chunks off the grid: entry i is (digest i, ranges_dev[i]).
+// insert: digests pairwise distinct. probe: src_addr_dev[i] is the address of a
+// resident chunk with digest i and length ranges_dev[i].len, or 0. gather: one
+// workgroup per chunk with src_addr_dev[i] != 0 copies it to
+// dst_base + ranges_dev[i].at, whatever the 16 B phases of the two.
+hipError_t modelx_dedup_insert_ranges(const void* digests_dev,
+                                      const modelx::abi::DedupRange* ranges_dev, uint32_t n,
+                                      void* table, uint64_t cap, uint32_t* dropped_dev,
+                                      hipStream_t stream);
+hipError_t modelx_dedup_probe_ranges(const void* digests_dev,
+                                     const modelx::abi::DedupRange* ranges_dev, uint32_t n,
+                                     const void* table, uint64_t cap, uint64_t* src_addr_dev,
+                                     hipStream_t stream);
+hipError_t modelx_dedup_gather_ranges(const uint64_t* src_addr_dev,
+                                      const modelx::abi::DedupRange* ranges_dev, uint32_t n,
+                                      uint64_t dst_base, hipStream_t stream);
+// Candidate positions (modelx/cdc_core.hpp) of the `len` bytes at `ptr`, per
+// tile: counts_dev[k] is tile k's true count, lists_dev[k * cap ...] holds
+// min(count, cap) of its hits in no order, each as the offset from the tile's
+// first grid address. ntiles must be cdc_tile_count(ptr, len), cap at most
+// kCdcMaxTileCap. Reads no byte outside the range.
+hipError_t modelx_cdc_candidates(const void* ptr, uint64_t len, uint32_t bits, uint32_t ntiles,
+                                 uint32_t cap, uint32_t* counts_dev, uint16_t* lists_dev,
+                                 hipStream_t stream);
 // Byte-plane split (merge == 0) or merge of `size` bytes, src -> dst, which
 // must not overlap (modelx/byteplane_host.hpp defines the transform).
 // hipErrorInvalidValue unless elem is 2, 4 or 8 and group a positive

@@ -26,6 +26,7 @@
 #include <pybind11/pybind11.h>
 #include <pybind11/stl.h>
 
+#include <algorithm>
 #include <atomic>
 #include <chrono>
 #include <condition_variable>
@@ -42,6 +43,7 @@
 #include <vector>
 
 #include "modelx/byteplane_host.hpp"
+#include "modelx/cdc_core.hpp"
 #include "modelx/crc32c_core.hpp"
 #include "modelx/device_abi.hpp"
 #include "modelx/http.hpp"
@@ -54,6 +56,7 @@ using namespace modelx;
 using modelx::abi::ChunkLeavesDesc;
 using modelx::abi::CopySeg;
 using modelx::abi::CrcRange;
+using modelx::abi::DedupRange;
 using modelx::abi::kDedupMaxProbes;
 using modelx::abi::PackSeg;
 using modelx::abi::TarEntry;
@@ -92,6 +95,28 @@ double now_s() {
 // the one leaf of the empty string.
 uint64_t expected_leaf_count(uint64_t size, uint64_t chunk_size) {
   return size ? (size - 1) / chunk_size + 1 : 1;
+}
+
+// CDC parameters outside cdc_core.hpp's valid range are refused at every
+// entry point with the same words.
+void check_cdc_params(const char* who, uint64_t min, uint64_t bits, uint64_t max) {
+  if (!cdc::valid_params(min, bits, max))
+    throw std::invalid_argument(std::string(who) + ": UNSUPPORTED cdc parameters (min=" +
+                                std::to_string(min) + ", bits=" + std::to_string(bits) +
+                                ", max=" + std::to_string(max) + "): need 64 <= min <= max <= " +
+                                "16 MiB and 1 <= bits <= 24");
+}
+
+void check_cdc_bits(const char* who, uint64_t bits) {
+  if (!cdc::valid_bits(bits))
+    throw std::invalid_argument(std::string(who) + ": UNSUPPORTED cdc bits " +
+                                std::to_string(bits) + " (1..24)");
+}
+
+py::list ranges_to_py(const std::vector<std::pair<uint64_t, uint64_t>>& ranges) {
+  py::list out;
+  for (auto& r : ranges) out.append(py::make_tuple(r.first, r.second));
+  return out;
 }
 
 // Leaf count of a packed 32 B/leaf array, or a throw when it is not the
@@ -1139,15 +1164,7 @@ class GpuEngine {
     }
     uint32_t n = static_cast<uint32_t>(idx.size());
     std::lock_guard<std::mutex> lk(dedup_mu_);
-    if (!dedup_table_) {
-      // lazy init at default capacity
-      uint64_t cap = 1ull << 22;
-      dedup_table_ = DeviceBuffer(cap * 48);
-      HIP_CHECK(hipMemsetAsync(dedup_table_.get(), 0, cap * 48, hash_stream_));
-      dedup_cap_ = cap;
-      dedup_dropped_ = DeviceBuffer(sizeof(uint32_t));
-      HIP_CHECK(hipMemsetAsync(dedup_dropped_.get(), 0, sizeof(uint32_t), hash_stream_));
-    }
+    ensure_dedup_table();
     // one upload: n leaves (32 B each), then their n chunk indexes
     char* dleaves = ds_leaves_.reserve<char>(uniq.size());
     HIP_CHECK(hipMemcpyAsync(dleaves, uniq.data(), uniq.size(), hipMemcpyHostToDevice,
@@ -1204,6 +1221,119 @@ class GpuEngine {
     py::list out;
     for (auto& m : missing) out.append(py::make_tuple(m.first, m.second));
     return py::make_tuple(out, deduped);
+  }
+
+  // The same for chunks off the grid (content-defined chunks): digest i
+  // belongs to the `length` bytes at base + offset of ranges[i]. Repeated
+  // digests are dropped on the host, first kept, as in dedup_register.
+  uint32_t dedup_register_ranges(py::bytes digests, uintptr_t base,
+                                 const std::vector<std::pair<uint64_t, uint64_t>>& ranges) {
+    std::string dv = digests;
+    checked_range_count("dedup_register_ranges", dv.size(), ranges.size());
+    HIP_CHECK(hipSetDevice(device_));
+    py::gil_scoped_release release;
+    std::string uniq;
+    std::vector<DedupRange> rs;
+    {
+      std::unordered_set<std::string_view> seen;
+      seen.reserve(ranges.size());
+      for (size_t i = 0; i < ranges.size(); i++) {
+        if (!ranges[i].second) continue;
+        if (!seen.insert(std::string_view(dv.data() + i * 32, 32)).second) continue;
+        uniq.append(dv.data() + i * 32, 32);
+        rs.push_back({base + ranges[i].first, ranges[i].second});
+      }
+    }
+    uint32_t n = static_cast<uint32_t>(rs.size());
+    std::lock_guard<std::mutex> lk(dedup_mu_);
+    ensure_dedup_table();
+    char* ddig = ds_leaves_.reserve<char>(std::max<size_t>(uniq.size(), 1));
+    DedupRange* dranges = ds_len_.reserve<DedupRange>(std::max<size_t>(n, 1) * sizeof(DedupRange));
+    if (n) {
+      HIP_CHECK(hipMemcpyAsync(ddig, uniq.data(), uniq.size(), hipMemcpyHostToDevice,
+                               hash_stream_));
+      HIP_CHECK(hipMemcpyAsync(dranges, rs.data(), n * sizeof(DedupRange),
+                               hipMemcpyHostToDevice, hash_stream_));
+      HIP_CHECK(modelx_dedup_insert_ranges(ddig, dranges, n, dedup_table_.get(), dedup_cap_,
+                                           dedup_dropped_.get<uint32_t>(), hash_stream_));
+    }
+    uint32_t dropped = 0;
+    HIP_CHECK(hipStreamSynchronize(hash_stream_));
+    HIP_CHECK(hipMemcpy(&dropped, dedup_dropped_.get(), sizeof dropped, hipMemcpyDeviceToHost));
+    return dropped;
+  }
+
+  // Probe + gather for a chunk list off the grid: chunk i (digest i) belongs
+  // at dst_ptr + offset of ranges[i]. Returns (missing (offset, length) ranges,
+  // coalesced where adjacent, deduped_bytes). The caller vouches that every
+  // range lies inside the destination.
+  py::tuple dedup_pull_ranges(py::bytes digests,
+                              const std::vector<std::pair<uint64_t, uint64_t>>& ranges,
+                              uintptr_t dst_ptr) {
+    std::string dv = digests;
+    uint32_t n = checked_range_count("dedup_pull_ranges", dv.size(), ranges.size());
+    std::vector<uint64_t> haddr(n, 0);
+    if (n && dedup_table_) {
+      HIP_CHECK(hipSetDevice(device_));
+      py::gil_scoped_release release;
+      std::vector<DedupRange> rs(n);
+      for (uint32_t i = 0; i < n; i++) rs[i] = {ranges[i].first, ranges[i].second};
+      std::lock_guard<std::mutex> lk(dedup_mu_);
+      void* ddig = ds_leaves_.reserve(dv.size());
+      DedupRange* dranges = ds_len_.reserve<DedupRange>(n * sizeof(DedupRange));
+      uint64_t* daddr = ds_addr_.reserve<uint64_t>((uint64_t)n * 8);
+      HIP_CHECK(hipMemcpyAsync(ddig, dv.data(), dv.size(), hipMemcpyHostToDevice, hash_stream_));
+      HIP_CHECK(hipMemcpyAsync(dranges, rs.data(), n * sizeof(DedupRange), hipMemcpyHostToDevice,
+                               hash_stream_));
+      HIP_CHECK(modelx_dedup_probe_ranges(ddig, dranges, n, dedup_table_.get(), dedup_cap_,
+                                          daddr, hash_stream_));
+      HIP_CHECK(modelx_dedup_gather_ranges(daddr, dranges, n, dst_ptr, hash_stream_));
+      HIP_CHECK(hipStreamSynchronize(hash_stream_));
+      HIP_CHECK(hipMemcpy(haddr.data(), daddr, (uint64_t)n * 8, hipMemcpyDeviceToHost));
+    }
+    std::vector<std::pair<uint64_t, uint64_t>> missing;
+    uint64_t deduped = 0;
+    for (uint32_t i = 0; i < n; i++) {
+      auto [off, ln] = ranges[i];
+      if (!ln) continue;
+      if (haddr[i] != 0) {
+        deduped += ln;
+      } else if (!missing.empty() && missing.back().first + missing.back().second == off) {
+        missing.back().second += ln;
+      } else {
+        missing.emplace_back(off, ln);
+      }
+    }
+    return py::make_tuple(ranges_to_py(missing), deduped);
+  }
+
+  // ------------------------------------------- content-defined chunking ----
+  // Candidate kernel on hash_stream_ (core/hip/cdc.hip) under cdc_mu_, the
+  // per-tile lists copied back and sorted here; a tile whose list overflowed
+  // is read back with its 31-byte halo and recomputed by cdc_core.hpp's loop,
+  // so the result is the host model's whatever the list capacity.
+
+  std::vector<uint64_t> cdc_candidates(uintptr_t ptr, uint64_t size, uint32_t bits) {
+    check_cdc_bits("cdc_candidates", bits);
+    if (size && (ptr == 0 || ptr > UINTPTR_MAX - size))
+      throw std::runtime_error("cdc_candidates: range is null or wraps the address space");
+    HIP_CHECK(hipSetDevice(device_));
+    py::gil_scoped_release release;
+    return cdc_candidates_impl(ptr, size, bits);
+  }
+
+  py::list cdc_chunks(uintptr_t ptr, uint64_t size, uint64_t min, uint64_t bits, uint64_t max) {
+    check_cdc_params("cdc_chunks", min, bits, max);
+    if (size && (ptr == 0 || ptr > UINTPTR_MAX - size))
+      throw std::runtime_error("cdc_chunks: range is null or wraps the address space");
+    HIP_CHECK(hipSetDevice(device_));
+    std::vector<std::pair<uint64_t, uint64_t>> out;
+    {
+      py::gil_scoped_release release;
+      out = cdc::select(cdc_candidates_impl(ptr, size, static_cast<uint32_t>(bits)), size, min,
+                        max);
+    }
+    return ranges_to_py(out);
   }
 
   void synchronize() {
@@ -1326,6 +1456,70 @@ class GpuEngine {
     return true;
   }
 
+  // dedup_mu_ held. Lazy init at the default capacity.
+  void ensure_dedup_table() {
+    if (dedup_table_) return;
+    uint64_t cap = 1ull << 22;
+    dedup_table_ = DeviceBuffer(cap * 48);
+    HIP_CHECK(hipMemsetAsync(dedup_table_.get(), 0, cap * 48, hash_stream_));
+    dedup_cap_ = cap;
+    dedup_dropped_ = DeviceBuffer(sizeof(uint32_t));
+    HIP_CHECK(hipMemsetAsync(dedup_dropped_.get(), 0, sizeof(uint32_t), hash_stream_));
+  }
+
+  static uint32_t checked_range_count(const char* who, size_t digest_bytes, size_t nranges) {
+    if (digest_bytes != nranges * 32 || nranges > UINT32_MAX)
+      throw std::runtime_error(std::string(who) + ": " + std::to_string(digest_bytes) +
+                               " digest bytes for " + std::to_string(nranges) + " ranges");
+    return static_cast<uint32_t>(nranges);
+  }
+
+  std::vector<uint64_t> cdc_candidates_impl(uintptr_t ptr, uint64_t size, uint32_t bits) {
+    std::vector<uint64_t> cand;
+    if (!size) return cand;
+    constexpr uint64_t kTile = modelx::abi::kCdcTileBytes;
+    const uint64_t phase = modelx::abi::cdc_tile_phase(ptr);
+    const uint64_t ntiles64 = modelx::abi::cdc_tile_count(ptr, size);
+    if (ntiles64 > UINT32_MAX) throw std::runtime_error("cdc: range too large for one call");
+    const uint32_t ntiles = static_cast<uint32_t>(ntiles64);
+    const uint32_t cap = modelx::abi::cdc_tile_cap(bits);
+    std::vector<uint32_t> counts(ntiles);
+    std::vector<uint16_t> lists(static_cast<size_t>(ntiles) * cap);
+    {
+      std::lock_guard<std::mutex> lk(cdc_mu_);
+      uint32_t* dcounts = cd_counts_.reserve<uint32_t>(ntiles * sizeof(uint32_t));
+      uint16_t* dlists = cd_lists_.reserve<uint16_t>(lists.size() * sizeof(uint16_t));
+      HIP_CHECK(modelx_cdc_candidates(reinterpret_cast<const void*>(ptr), size, bits, ntiles, cap,
+                                      dcounts, dlists, hash_stream_));
+      HIP_CHECK(hipStreamSynchronize(hash_stream_));
+      HIP_CHECK(hipMemcpy(counts.data(), dcounts, ntiles * sizeof(uint32_t),
+                          hipMemcpyDeviceToHost));
+      HIP_CHECK(hipMemcpy(lists.data(), dlists, lists.size() * sizeof(uint16_t),
+                          hipMemcpyDeviceToHost));
+    }
+    std::string halo_and_tile;
+    for (uint32_t k = 0; k < ntiles; k++) {
+      // positions [first, last) of the range are tile k's; grid offset g of
+      // the tile is position k * kTile + g - phase
+      const uint64_t first = k ? k * kTile - phase : 0;
+      const uint64_t last = std::min<uint64_t>((k + 1) * kTile - phase, size);
+      const size_t before = cand.size();
+      if (counts[k] <= cap) {
+        const uint16_t* l = lists.data() + static_cast<size_t>(k) * cap;
+        for (uint32_t i = 0; i < counts[k]; i++) cand.push_back(k * kTile + l[i] - phase);
+        std::sort(cand.begin() + before, cand.end());
+      } else {
+        const uint64_t from = first >= cdc::kWindow - 1 ? first - (cdc::kWindow - 1) : 0;
+        halo_and_tile.resize(last - from);
+        HIP_CHECK(hipMemcpy(&halo_and_tile[0], reinterpret_cast<const void*>(ptr + from),
+                            last - from, hipMemcpyDeviceToHost));
+        cdc::candidates(reinterpret_cast<const uint8_t*>(halo_and_tile.data()), last - from, bits,
+                        from, first - from, &cand);
+      }
+    }
+    return cand;
+  }
+
   int device_;
   size_t slot_bytes_;
   std::atomic<int> push_rr_{0};
@@ -1353,6 +1547,8 @@ class GpuEngine {
   DeviceScratch ds_leaves_, ds_addr_, ds_len_;
   std::mutex crc_mu_;  // guards the crc32c_ranges scratch below
   DeviceScratch cs_descs_, cs_segs_, cs_out_;
+  std::mutex cdc_mu_;  // guards the candidate kernel's scratch below
+  DeviceScratch cd_counts_, cd_lists_;
 };
 
 bool hip_available() {
@@ -1410,6 +1606,15 @@ PYBIND11_MODULE(_core, m) {
            py::arg("chunk_size"), py::arg("total"))
       .def("dedup_pull", &GpuEngine::dedup_pull, py::arg("expect"), py::arg("dst_ptr"),
            py::arg("chunk_size"), py::arg("total"))
+      .def("dedup_register_ranges", &GpuEngine::dedup_register_ranges, py::arg("digests"),
+           py::arg("base_ptr"), py::arg("ranges"))
+      .def("dedup_pull_ranges", &GpuEngine::dedup_pull_ranges, py::arg("digests"),
+           py::arg("ranges"), py::arg("dst_ptr"))
+      .def("cdc_candidates", &GpuEngine::cdc_candidates, py::arg("ptr"), py::arg("size"),
+           py::arg("bits"))
+      .def("cdc_chunks", &GpuEngine::cdc_chunks, py::arg("ptr"), py::arg("size"),
+           py::arg("min") = (uint64_t)cdc::kDefaultMin, py::arg("bits") = (uint64_t)cdc::kDefaultBits,
+           py::arg("max") = (uint64_t)cdc::kDefaultMax)
       .def("zstd_decompress_many", &GpuEngine::zstd_decompress_many, py::arg("items"))
       .def("sha256_chunk_leaves_many", &GpuEngine::sha256_chunk_leaves_many,
            py::arg("items"))
@@ -1517,6 +1722,36 @@ PYBIND11_MODULE(_core, m) {
   m.def("crc32c_combine", &crc32c::combine, py::arg("crc_a"), py::arg("crc_b"),
         py::arg("len_b"));
   m.attr("CRC32C_SEGMENT_BYTES") = modelx::abi::kCrc32cSegmentBytes;
+  // Content-defined chunking on host bytes (cdc_core.hpp): the model of
+  // GpuEngine::cdc_candidates / cdc_chunks, and their overflow path.
+  m.def(
+      "cdc_candidates_host",
+      [](py::bytes data, uint32_t bits) {
+        check_cdc_bits("cdc_candidates_host", bits);
+        std::string_view s = data;
+        std::vector<uint64_t> out;
+        py::gil_scoped_release release;
+        cdc::candidates(reinterpret_cast<const uint8_t*>(s.data()), s.size(), bits, 0, 0, &out);
+        return out;
+      },
+      py::arg("data"), py::arg("bits"));
+  m.def(
+      "cdc_chunks_host",
+      [](py::bytes data, uint64_t min, uint64_t bits, uint64_t max) {
+        check_cdc_params("cdc_chunks_host", min, bits, max);
+        std::string_view s = data;
+        std::vector<std::pair<uint64_t, uint64_t>> out;
+        {
+          py::gil_scoped_release release;
+          out = cdc::chunks(reinterpret_cast<const uint8_t*>(s.data()), s.size(), min,
+                            static_cast<uint32_t>(bits), max);
+        }
+        return ranges_to_py(out);
+      },
+      py::arg("data"), py::arg("min") = (uint64_t)cdc::kDefaultMin,
+      py::arg("bits") = (uint64_t)cdc::kDefaultBits, py::arg("max") = (uint64_t)cdc::kDefaultMax);
+  m.attr("CDC_DEFAULTS") = py::make_tuple(cdc::kDefaultMin, cdc::kDefaultBits, cdc::kDefaultMax);
+  m.attr("CDC_TILE_BYTES") = modelx::abi::kCdcTileBytes;
   // One-shot GET through the NATIVE http client (the exact code path the
   // engine's ranged fetches use, incl. TLS) — lets the GPU-less suite prove
   // https presigned-URL support against a TLS server.

@@ -51,10 +51,10 @@ def main(argv=None) -> int:
         from ..client.fanout import fanout_pull_single_process
         from ..wire import types as wt
 
-        # leaves sidecars are pull metadata, not model content — don't
-        # land them as HBM tensors
+        # leaves and CDC sidecars are pull metadata, not model content —
+        # don't land them as HBM tensors
         gpu_sel = [b for b in selection
-                   if b.media_type != wt.MEDIA_TYPE_MODEL_LEAVES]
+                   if b.media_type not in wt.SIDECAR_MEDIA_TYPES]
         tensors = fanout_pull_single_process(ref, manifest, gpu_sel, devices)
         for dev, named in tensors.items():
             for name, t in named.items():

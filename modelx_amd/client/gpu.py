@@ -165,7 +165,9 @@ class _Landing(NamedTuple):
 # One digested device blob ready for upload: `digest` is the main digest, `root`
 # the chunked one, `notes` the annotations beyond the chunk ones. `keep` holds the
 # compressed tensor alive until pushed (None: `ptr` is the source tensor's memory).
-_PushBlob = namedtuple("_PushBlob", "name ptr size media_type digest root leaves notes keep")
+# `cdc` is the body of the blob's CDC sidecar, b"" without one.
+_PushBlob = namedtuple("_PushBlob", "name ptr size media_type digest root leaves notes keep cdc",
+                       defaults=(b"",))
 
 
 class GpuClient:
@@ -174,11 +176,17 @@ class GpuClient:
 
     PART_RETRIES = 3  # reference: pkg/client/extension_s3.go:133-148
     ZSTD_WAVE_CAP = 64 << 30  # raw bytes per batched-decode wave
+    cdc = None  # (min, bits, max) of content-defined chunking; set per instance
 
     def __init__(self, registry: str, authorization: str = "", device: int = 0,
                  num_slots: int = DEFAULT_NUM_SLOTS, slot_bytes: int = DEFAULT_SLOT_BYTES,
-                 num_conns: int = DEFAULT_NUM_CONNS, dedup: bool = False):
+                 num_conns: int = DEFAULT_NUM_CONNS, dedup: bool = False, cdc=False):
         core = _core()
+        # shift-tolerant dedup: with ``dedup``, blobs are also registered and
+        # looked up by content-defined chunks (core/hip/cdc.hip), so resident
+        # bytes are found wherever an insertion moved them. True, or
+        # (min, bits, max); None when off.
+        self.cdc = rules.cdc_params(cdc)
         if not core.hip_available():
             raise er.ModelxError(er.ErrCode.INTERNAL, "no HIP device visible")
         self.remote = RegistryClient(registry, authorization)
@@ -341,20 +349,60 @@ class GpuClient:
     # ------------------------------------------------------ chunk dedup --
 
     def register_chunks(self, tensor, leaves: bytes, chunk_size: int,
-                        size: Optional[int] = None) -> None:
+                        size: Optional[int] = None, cdc=None) -> None:
         """Add a blob's chunks to the HBM dedup table (dedup.hip insert
         kernel); keeps the tensor alive while registered. ``size`` is the
-        blob's length when the tensor is larger than the blob it holds."""
+        blob's length when the tensor is larger than the blob it holds.
+
+        A client with ``cdc`` also registers the blob's content-defined
+        chunks, cut from the bytes themselves at ``cdc`` (the parameters of
+        the blob's sidecar) or else the client's own, so a blob pushed
+        without a sidecar still becomes a source."""
         if not self.dedup:
             return
         nbytes = tensor.numel() * tensor.element_size()
         if size is None:
             size = nbytes
-        if size > nbytes or not leaves_usable(leaves, size, chunk_size):
+        if size > nbytes:
             return  # would index chunks the tensor does not have
-        self._dedup_tensors.append(tensor)
-        self.engine.dedup_register(leaves, tensor.data_ptr(), chunk_size, size)
-        self._dedup_registered = True
+        if leaves_usable(leaves, size, chunk_size):
+            self._dedup_tensors.append(tensor)
+            self.engine.dedup_register(leaves, tensor.data_ptr(), chunk_size, size)
+            self._dedup_registered = True
+        if self.cdc and size:
+            ranges, digests = self._cdc_chunk_digests(tensor.data_ptr(), size, cdc or self.cdc)
+            self._dedup_tensors.append(tensor)
+            self.engine.dedup_register_ranges(digests, tensor.data_ptr(), ranges)
+            self._dedup_registered = True
+
+    def _cdc_chunk_digests(self, ptr: int, size: int, params) -> Tuple[list, bytes]:
+        """The content-defined chunks of device memory and their SHA-256:
+        boundaries from the candidate kernel (core/hip/cdc.hip), one hash
+        chain per chunk (``sha256_multibuf``)."""
+        ranges = self.engine.cdc_chunks(ptr, size, *params)
+        return ranges, self.engine.sha256_multibuf([(ptr + off, ln) for off, ln in ranges])
+
+    def _usable_cdc(self, job: "_Landing"):
+        """``(params, ranges, digests)`` from the blob's CDC sidecar, None
+        when it has none or ``rules.cdc_usable`` rejects it."""
+        note = job.desc.annotations.get(types.ANNOTATION_CDC_BLOB, "")
+        if not note:
+            return None
+        try:
+            data = b"".join(self.remote.get_blob_content(job.repository, note))
+        except er.ModelxError:
+            return None
+        return rules.cdc_usable(data, note, job.desc.size)
+
+    def _register_landed(self, job: "_Landing", leaves: bytes, side=None) -> None:
+        """Register a landed, digest-checked blob as a dedup source: on the
+        grid by ``leaves``, and with ``cdc`` by content-defined chunks at the
+        parameters of its usable sidecar (``side`` if already read)."""
+        params = None
+        if self.dedup and self.cdc:
+            side = side or self._usable_cdc(job)
+            params = side[0] if side else None
+        self.register_chunks(job.tensor, leaves, job.cs, job.desc.size, params)
 
     def clear_chunk_index(self) -> None:
         if self._dedup_registered:
@@ -388,6 +436,8 @@ class GpuClient:
         out = None
         if resume and had_tensor:
             out = self._land_resume(job)
+        if out is None and self.dedup and self.cdc and self._dedup_registered:
+            out = self._land_cdc(job)
         if out is None and self.dedup and self._dedup_registered:
             out = self._land_dedup(job)
         if out is None:
@@ -479,7 +529,33 @@ class GpuClient:
             if target and root != target[0]:
                 raise er.ModelxError(er.ErrCode.DIGEST_INVALID,
                                      f"GPU chunk digest mismatch for {desc.name}: {root}")
-        self.register_chunks(job.tensor, expect, cs, desc.size)
+        self._register_landed(job, expect)
+        return job.tensor
+
+    def _land_cdc(self, job: _Landing) -> Optional["torch.Tensor"]:
+        """Shift-tolerant dedup: look the chunks of the blob's CDC sidecar up
+        in the HBM table and gather the resident ones D2D wherever they lie
+        (dedup.hip's off-grid kernels), fetch only the rest. The sidecar is
+        never trusted: the blob's ordinary digest decides, and a mismatch (a
+        stale or poisoned table entry) takes the chunk refetch. None without
+        a usable sidecar or when no chunk is resident."""
+        side = self._usable_cdc(job)
+        if side is None:
+            return None
+        _, ranges, digests = side
+        t0 = time.monotonic()
+        missing, dedup_bytes = self.engine.dedup_pull_ranges(digests, ranges, job.ptr)
+        if not dedup_bytes:
+            return None
+        fetched = self._fetch_ranges(job.url, job.headers, job.ptr, missing)
+        self._stat("pull-cdc", fetched, t0, name=job.desc.name, dedup_bytes=dedup_bytes,
+                   chunks=len(ranges))
+        if job.verify:
+            try:
+                self._verify_device_digest(job.ptr, job.desc.size, job.desc)
+            except er.ModelxError as first_err:
+                self._refetch_bad_chunks(job, first_err)
+            self._register_landed(job, self._usable_leaves(job) or b"", side)
         return job.tensor
 
     def _land_transfer(self, job: _Landing) -> "torch.Tensor":
@@ -498,7 +574,7 @@ class GpuClient:
             if dg.root_from_leaf_bytes(leaves, cs, desc.size) == target[0]:
                 self.last_stats.append({"phase": "pull-verify", "bytes": desc.size,
                                         "seconds": time.monotonic() - t0 - stats["seconds"]})
-                self.register_chunks(job.tensor, leaves, cs, desc.size)
+                self._register_landed(job, leaves)
                 return job.tensor
         else:
             stats = self.engine.pull_to_device(job.url, job.headers, desc.size, job.ptr,
@@ -1088,9 +1164,9 @@ class GpuClient:
 
     def _upload_blob(self, repository: str, blob: _PushBlob, chunk_size: int,
                      part_bytes: int, now,
-                     part_checksum: str = "") -> Tuple[types.Descriptor, types.Descriptor]:
-        """Upload a digested blob and its leaves sidecar; returns both
-        descriptors. The sidecar (32 B per chunk) enables chunk-level
+                     part_checksum: str = "") -> Tuple[types.Descriptor, ...]:
+        """Upload a digested blob and its sidecars (leaves, and CDC when the
+        blob carries one); returns their descriptors, the blob's first. The sidecar (32 B per chunk) enables chunk-level
         resume/refetch/dedup on pull; it is listed in the manifest so GC
         keeps it, with its own media type so clients can skip it."""
         leaves_digest = dg.sha256_digest(blob.leaves)
@@ -1109,7 +1185,27 @@ class GpuClient:
         ldesc = types.Descriptor(
             name=blob.name + ".leaves", media_type=types.MEDIA_TYPE_MODEL_LEAVES,
             digest=leaves_digest, size=len(blob.leaves), modified=now)
-        return desc, self._upload_small_once(repository, ldesc, blob.leaves, part_checksum)
+        descs = (desc, self._upload_small_once(repository, ldesc, blob.leaves, part_checksum))
+        if blob.cdc:
+            # the CDC sidecar travels exactly like the leaves one
+            cdesc = types.Descriptor(
+                name=blob.name + ".cdc", media_type=types.MEDIA_TYPE_MODEL_CDC,
+                digest=desc.annotations[types.ANNOTATION_CDC_BLOB], size=len(blob.cdc),
+                modified=now)
+            descs += (self._upload_small_once(repository, cdesc, blob.cdc, part_checksum),)
+        return descs
+
+    def _with_cdc_sidecar(self, blob: _PushBlob, params) -> _PushBlob:
+        """``blob`` with its CDC sidecar built from the source bytes in HBM
+        (producers are synchronised by the digest that came before)."""
+        if not params or not blob.size:
+            return blob
+        t0 = time.monotonic()
+        ranges, digests = self._cdc_chunk_digests(blob.ptr, blob.size, params)
+        body = rules.cdc_sidecar(params, ranges, digests)
+        self._stat("push-cdc", blob.size, t0, name=blob.name, chunks=len(ranges))
+        notes = {**blob.notes, types.ANNOTATION_CDC_BLOB: dg.sha256_digest(body)}
+        return blob._replace(notes=notes, cdc=body)
 
     def push_from_gpu(self, repository: str, version: str,
                       tensors: Dict[str, "torch.Tensor"], config_yaml: str = "",
@@ -1117,7 +1213,7 @@ class GpuClient:
                       part_bytes: int = DEFAULT_PART_BYTES,
                       compress: str = "", digest_mode: str = "chunked",
                       dirs: Optional[Dict[str, Dict[str, "torch.Tensor"]]] = None,
-                      planes=0, part_checksum: str = "") -> types.Manifest:
+                      planes=0, part_checksum: str = "", cdc=False) -> types.Manifest:
         """Digest on GPU → presigned multipart upload → manifest PUT last.
         With ``compress="zstd"`` each tensor is compressed on-GPU into a
         seekable multi-frame zstd blob (core/hip/zstd.hip) first; the
@@ -1164,10 +1260,25 @@ class GpuClient:
         (core/hip/crc32c.hip, ``push_blob_from_device``), the config and the
         leaves sidecars theirs from the host. Blobs that travel through the
         registry (no presigned location) are not covered. The kernel's time
-        is the ``push-part-checksum`` phase of ``last_stats``."""
+        is the ``push-part-checksum`` phase of ``last_stats``.
+
+        ``cdc`` is ``False``, ``True`` (min 32 KiB, 16 bits, max 256 KiB) or
+        ``(min, bits, max)``. With it every blob, directory archives included,
+        is cut into content-defined chunks on the GPU (core/hip/cdc.hip), each
+        chunk hashed, and the list uploaded as a CDC sidecar named by the
+        ``modelx.amd/cdc-blob`` annotation: a ``GpuClient(dedup=True,
+        cdc=...)`` that pulls the blob gathers every chunk it already holds
+        in HBM, wherever an insertion or a resized tensor moved it. Not
+        available with ``compress="zstd"``. Its time is the ``push-cdc``
+        phase of ``last_stats``."""
         rules.check_part_checksum(part_checksum)
+        cdc_params = rules.cdc_params(cdc)
         if compress not in ("", "zstd"):
             raise er.ModelxError(er.ErrCode.UNSUPPORTED, f"unknown compression {compress!r}")
+        if cdc_params and compress:
+            raise er.ModelxError(er.ErrCode.UNSUPPORTED,
+                                 "cdc cannot be combined with compress: chunking "
+                                 "compressed frames finds no shifted content")
         if digest_mode not in ("chunked", "sha256"):
             raise er.ModelxError(er.ErrCode.UNSUPPORTED, f"unknown digest_mode {digest_mode!r}")
         if planes != "auto":
@@ -1179,7 +1290,10 @@ class GpuClient:
                 raise er.ModelxError(er.ErrCode.UNSUPPORTED,
                                      "dirs cannot be combined with compress: "
                                      "there is no tar+zstd directory media type")
-            rules.check_dir_names(tensors, dirs)
+            if cdc_params:
+                rules.check_dir_names(tensors, dirs, cdc=True)
+            else:
+                rules.check_dir_names(tensors, dirs)
             # pack (and thereby validate) every directory before the first
             # upload; the archives then travel as ordinary device blobs
             tensors = dict(tensors)
@@ -1207,14 +1321,15 @@ class GpuClient:
             # only until it is pushed
             blob = self._digest_one(name, tensors[name], chunk_size, digest_mode,
                                     media_type_of(name), compress, planes)
-            descs = upload(blob)
+            descs = upload(self._with_cdc_sidecar(blob, cdc_params))
             if blob.keep is None:
                 self.register_chunks(tensors[name], blob.leaves, chunk_size)
             return descs
 
         if compress == "" and len(tensors) > 1:
             # many-blob fast path: one batched digest, uploads in parallel
-            blobs = self._digest_batched(tensors, chunk_size, digest_mode, media_type_of)
+            blobs = [self._with_cdc_sidecar(b, cdc_params) for b in
+                     self._digest_batched(tensors, chunk_size, digest_mode, media_type_of)]
             pushed = _map(upload, blobs, DEFAULT_PUSH_PARALLEL)
             for blob in blobs:
                 self.register_chunks(tensors[blob.name], blob.leaves, chunk_size)

@@ -7,6 +7,7 @@ here, so a rule read in two places cannot drift apart.
 from __future__ import annotations
 
 import base64
+import struct
 from typing import Dict, List, Optional, Tuple
 
 from ..wire import digest as dg
@@ -37,6 +38,80 @@ def leaves_usable(leaves, size: int, chunk_size) -> bool:
         return False
     want = (size - 1) // chunk_size + 1 if size else 1
     return len(leaves) == 32 * want
+
+
+# Content-defined chunking (core/include/modelx/cdc_core.hpp): (min, bits, max)
+CDC_DEFAULTS = (32 << 10, 16, 256 << 10)
+CDC_MAGIC = b"MXCDC1\0\0"
+_CDC_HEADER = struct.Struct("<8sIIII")
+_CDC_RECORD = 4 + 32
+
+
+def _cdc_valid(params) -> bool:
+    if not isinstance(params, (tuple, list)) or len(params) != 3:
+        return False
+    if any(isinstance(v, bool) or not isinstance(v, int) for v in params):
+        return False
+    lo, bits, hi = params
+    return 64 <= lo <= hi <= (16 << 20) and 1 <= bits <= 24
+
+
+def cdc_params(cdc) -> Optional[Tuple[int, int, int]]:
+    """The ``cdc`` option of ``GpuClient`` and ``push_from_gpu``: ``False``
+    or ``None`` (off, returns None), ``True`` (the defaults) or
+    ``(min, bits, max)``; invalid parameters are UNSUPPORTED."""
+    if cdc is None or cdc is False:
+        return None
+    if cdc is True:
+        return CDC_DEFAULTS
+    if not _cdc_valid(cdc):
+        raise er.ModelxError(er.ErrCode.UNSUPPORTED,
+                             f"unsupported cdc parameters {cdc!r}: need (min, bits, max) with "
+                             "64 <= min <= max <= 16 MiB and 1 <= bits <= 24")
+    return tuple(cdc)
+
+
+def cdc_sidecar(params, ranges, digests: bytes) -> bytes:
+    """The CDC sidecar body: header (magic, min, max, bits, count), then per
+    chunk its length and SHA-256. ``ranges`` are the blob's (offset, length)
+    chunks in order; offsets are implied by the lengths."""
+    lo, bits, hi = params
+    assert len(digests) == 32 * len(ranges)
+    out = [_CDC_HEADER.pack(CDC_MAGIC, lo, hi, bits, len(ranges))]
+    for i, (_, ln) in enumerate(ranges):
+        out.append(struct.pack("<I", ln) + digests[32 * i:32 * i + 32])
+    return b"".join(out)
+
+
+def cdc_usable(data, sidecar_digest: str, size: int):
+    """``(params, ranges, digests)`` of a CDC sidecar that describes a
+    ``size``-byte blob, else None. The sidecar arrives from the remote and its
+    ranges become device writes, so it counts as absent (the pull takes the
+    next strategy) unless its digest matches, its magic and parameters are
+    valid, every length is in 1..max and the lengths sum to ``size``."""
+    if not isinstance(data, (bytes, bytearray)) or not sidecar_digest:
+        return None
+    if dg.sha256_digest(bytes(data)) != sidecar_digest:
+        return None
+    if len(data) < _CDC_HEADER.size:
+        return None
+    magic, lo, hi, bits, count = _CDC_HEADER.unpack_from(data)
+    if magic != CDC_MAGIC or not _cdc_valid((lo, bits, hi)):
+        return None
+    if len(data) != _CDC_HEADER.size + count * _CDC_RECORD:
+        return None
+    ranges, digests, off = [], [], 0
+    for i in range(count):
+        at = _CDC_HEADER.size + i * _CDC_RECORD
+        ln, = struct.unpack_from("<I", data, at)
+        if ln == 0 or ln > hi:
+            return None
+        ranges.append((off, ln))
+        digests.append(bytes(data[at + 4:at + _CDC_RECORD]))
+        off += ln
+    if off != size:
+        return None
+    return (lo, bits, hi), ranges, b"".join(digests)
 
 
 def annotated_chunk_size(desc: types.Descriptor) -> int:
@@ -133,11 +208,11 @@ def zstd_waves(jobs: list, cap: int) -> List[list]:
 
 def payload_descriptors(manifest: types.Manifest,
                         skip_sidecars: bool = True) -> List[types.Descriptor]:
-    """The blobs of a manifest a pull lands: non-empty, and no leaves
-    sidecar (those are read on demand, never landed as payload)."""
+    """The blobs of a manifest a pull lands: non-empty, and no leaves or
+    CDC sidecar (those are read on demand, never landed as payload)."""
     return [d for d in manifest.blobs
             if d.size and not (skip_sidecars
-                               and d.media_type == types.MEDIA_TYPE_MODEL_LEAVES)]
+                               and d.media_type in types.SIDECAR_MEDIA_TYPES)]
 
 
 def split_payloads(descs, expand_dirs: bool = False) -> Tuple[list, list, list]:
@@ -177,17 +252,19 @@ def part_checksum_headers(crc: int) -> Dict[str, str]:
     return {PART_CHECKSUM_HEADER: base64.b64encode(crc.to_bytes(4, "big")).decode()}
 
 
-def check_dir_names(tensors, dirs) -> None:
+def check_dir_names(tensors, dirs, cdc: bool = False) -> None:
     """Every descriptor name the manifest of a push will carry must be
-    unique: the config, each blob and each blob's leaves sidecar."""
+    unique: the config, each blob and each blob's leaves sidecar (and its
+    CDC sidecar in a push with ``cdc``)."""
+    suffixes = ("", ".leaves", ".cdc") if cdc else ("", ".leaves")
     taken = {"modelx.yaml"}
     for tname in tensors:
-        taken.update((tname, tname + ".leaves"))
+        taken.update(tname + sfx for sfx in suffixes)
     for dname in dirs:
         if "/" in dname:
             raise ValueError(f"directory name {dname!r} contains '/'")
-        for n in (dname, dname + ".leaves"):
+        for n in (dname + sfx for sfx in suffixes):
             if n in taken:
                 raise ValueError(f"directory {dname!r}: the name {n!r} is "
                                  "already used by another blob of this push")
-        taken.update((dname, dname + ".leaves"))
+        taken.update(dname + sfx for sfx in suffixes)

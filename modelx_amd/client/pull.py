@@ -75,7 +75,7 @@ class Puller:
         if desc.media_type in (types.MEDIA_TYPE_MODEL_DIRECTORY_TARGZ,
                                types.MEDIA_TYPE_MODEL_DIRECTORY_TAR):
             self._pull_directory(repository, desc, into_dir, bar, plan_blobs)
-        elif desc.media_type == types.MEDIA_TYPE_MODEL_LEAVES:
+        elif desc.media_type in types.SIDECAR_MEDIA_TYPES:
             if bar:
                 bar.set_status("sidecar", complete=True)
         elif desc.media_type == types.MEDIA_TYPE_MODEL_FILE_ZSTD:

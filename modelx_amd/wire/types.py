@@ -42,6 +42,13 @@ ANNOTATION_CHUNK_SIZE = "modelx.amd/chunk-size"
 ANNOTATION_LEAVES_BLOB = "modelx.amd/leaves-blob"
 # media type of a leaves blob (listed in the manifest so GC keeps it)
 MEDIA_TYPE_MODEL_LEAVES = "application/vnd.modelx.amd.leaves.v1"
+#   digest of the companion CDC blob: the blob's content-defined chunks
+#   (length + SHA-256 each), enabling shift-tolerant chunk dedup on pull
+ANNOTATION_CDC_BLOB = "modelx.amd/cdc-blob"
+# media type of a CDC blob (listed in the manifest so GC keeps it)
+MEDIA_TYPE_MODEL_CDC = "application/vnd.modelx.amd.cdc.v1"
+# sidecars are pull metadata, never model content: no pull lands or writes them
+SIDECAR_MEDIA_TYPES = (MEDIA_TYPE_MODEL_LEAVES, MEDIA_TYPE_MODEL_CDC)
 # uncompressed tar directory blob — GPU-scatterable without a CPU inflate
 # (optional alternative to ...directory.v1.tar+gz; reference clients treat it
 # as an opaque file)

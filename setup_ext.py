@@ -22,15 +22,18 @@ SOURCES = [
     "core/hip/zstd.hip",
     "core/hip/byteplane.hip",
     "core/hip/crc32c.hip",
+    "core/hip/cdc.hip",
     "core/src/zstd_cpu.cpp",
     "core/src/http.cpp",
     "core/src/json.cpp",
 ]
 
-# crc32c.hip is integer work throughout: keep the compiler from forming packed
-# fp32 instructions in it.
+# crc32c.hip and cdc.hip are integer work throughout: keep the compiler from
+# forming packed fp32 instructions in them.
+_NO_PACKED_FP32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 EXTRA_FLAGS = {
-    "core/hip/crc32c.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
+    "core/hip/crc32c.hip": _NO_PACKED_FP32,
+    "core/hip/cdc.hip": _NO_PACKED_FP32,
 }
 
 
