@@ -15,12 +15,17 @@
 //    memory, so the H2D DMA needs no extra copy
 //  - H2D copies run on a small pool of side streams, overlapped with the
 //    next range's socket reads; a reclaimer thread returns slots on event
-//    completion, so the ring never blocks a downloader on DMA
-//  - after landing, the CDNA4 SHA-256 chunk kernel (core/hip/sha256.hip)
-//    verifies the chunked digest at HBM-class rate, off the transfer's
-//    critical path
+//    completion, so the ring never blocks a downloader on DMA; the copy
+//    streams carry copies only, so a slot is back in the ring as soon as its
+//    own H2D copy has ended
+//  - once the whole blob has landed, ONE launch of the CDNA4 SHA-256 chunk
+//    kernel (core/hip/sha256.hip) hashes it from HBM: every chunk chain of
+//    the blob in flight at once (~8 ms for 8 GiB) where a launch per 64 MiB
+//    slot is 512 chains on a near-idle chip (~7 ms each)
 //
 // The same ring runs push: device → pinned slot (D2H) → multipart PUT parts.
+// Every ring user takes ONE slot at a time and never waits for a slot while
+// holding one (SlotLease).
 #include <hip/hip_runtime.h>
 #include <openssl/evp.h>
 #include <pybind11/pybind11.h>
@@ -155,6 +160,7 @@ py::list indexed_files_to_py(const std::vector<tarhost::IndexedFile>& files) {
 struct Slot {
   char* host = nullptr;     // pinned
   hipEvent_t event = nullptr;
+  hipEvent_t event2 = nullptr;  // second half of a double-buffered drain (SlotLease)
   size_t bytes = 0;
 };
 
@@ -245,6 +251,7 @@ class GpuEngine {
       HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&s.host), slot_bytes,
                               hipHostMallocDefault));
       HIP_CHECK(hipEventCreateWithFlags(&s.event, hipEventDisableTiming));
+      HIP_CHECK(hipEventCreateWithFlags(&s.event2, hipEventDisableTiming));
       free_.push(&s);
     }
     streams_.resize(num_streams);
@@ -259,6 +266,7 @@ class GpuEngine {
     hipEventDestroy(zs_staged_);
     for (auto& s : slots_) {
       if (s.event) hipEventDestroy(s.event);
+      if (s.event2) hipEventDestroy(s.event2);
       if (s.host) hipHostFree(s.host);
     }
   }
@@ -294,11 +302,12 @@ class GpuEngine {
     return pull_impl(url, headers, total, dst_ptr, num_conns, 0, 0, &leaves, &rs);
   }
 
-  // Same, but ALSO hashes every landed slot with the CDNA4 SHA-256 chunk
-  // kernel on the slot's own stream right after its H2D copy — verification
-  // overlaps the remaining transfer ("verify as chunks land"). Returns
-  // (stats, leaves). slot_bytes must be a chunk_size multiple (64 MiB / 128
-  // KiB is), so every slot covers whole chunks.
+  // Same, but ALSO hashes the landed blob with the CDNA4 SHA-256 chunk
+  // kernel: one launch over [dst_ptr, dst_ptr+size) once every copy has
+  // ended, so the copy streams carry copies only and each slot returns to
+  // the ring when its own copy is done. Returns (stats, leaves); an empty
+  // blob has the one leaf of the empty string. slot_bytes must be a
+  // chunk_size multiple (64 MiB / 128 KiB is).
   py::tuple pull_to_device_hashed(const std::string& url,
                                   const std::map<std::string, std::string>& headers,
                                   uint64_t size, uintptr_t dst_ptr, int num_conns,
@@ -346,6 +355,7 @@ class GpuEngine {
     std::string error;
     std::atomic<uint64_t> net_bytes{0};
     std::atomic<long> net_ns{0};
+    std::atomic<long> slot_wait_ns{0};
 
     // reclaimer: waits for H2D events, returns slots to the free pool
     std::atomic<bool> done_submitting{false};
@@ -406,7 +416,9 @@ class GpuEngine {
             ok = true;
             for (uint64_t poff = 0; poff < r.length && ok; poff += slot_bytes_) {
               uint64_t plen = std::min<uint64_t>(slot_bytes_, r.length - poff);
-              Slot* slot = acquire_slot();
+              double waited = 0;
+              Slot* slot = acquire_slot(&waited);
+              slot_wait_ns.fetch_add(static_cast<long>(waited * 1e9));
               if (!conn.read_body_exact(slot->host, plen)) {
                 conn.close_fd();
                 release_slot(slot);
@@ -417,15 +429,8 @@ class GpuEngine {
               hipStream_t st = streams_[stream_rr.fetch_add(1) % streams_.size()];
               hipError_t e = hipMemcpyAsync(reinterpret_cast<char*>(dst_ptr) + abs_off,
                                             slot->host, plen, hipMemcpyHostToDevice, st);
-              if (e == hipSuccess && hash_chunk) {
-                uint32_t first_chunk = static_cast<uint32_t>(abs_off / hash_chunk);
-                uint32_t n_chunks =
-                    static_cast<uint32_t>((plen + hash_chunk - 1) / hash_chunk);
-                e = modelx_sha256_chunk_leaves(
-                    reinterpret_cast<char*>(dst_ptr) + abs_off, plen, hash_chunk,
-                    dleaves.get<char>() + static_cast<size_t>(first_chunk) * 32,
-                    n_chunks, st);
-              }
+              // the event follows the copy directly: no kernel ever runs on
+              // a copy stream, so the slot is free when its copy has ended
               if (e == hipSuccess) e = hipEventRecord(slot->event, st);
               if (e != hipSuccess) {
                 {
@@ -463,7 +468,15 @@ class GpuEngine {
     cv_pending_.notify_all();
     reclaimer.join();
     for (auto& st : streams_) HIP_CHECK(hipStreamSynchronize(st));
-    if (hash_chunk) {
+    if (hash_chunk && error.empty()) {  // the workers have joined: no lock needed
+      // every byte is in HBM: one wide launch hashes all chunks at once. The
+      // stream is taken round-robin over the engine's streams so concurrent
+      // small pulls hash side by side; at this point it is idle for this
+      // pull, and the launch holds no slot.
+      hipStream_t hst = streams_[hash_rr_.fetch_add(1) % streams_.size()];
+      HIP_CHECK(modelx_sha256_chunk_leaves(reinterpret_cast<void*>(dst_ptr), size, hash_chunk,
+                                           dleaves.get(), total_chunks, hst));
+      HIP_CHECK(hipStreamSynchronize(hst));
       leaves_out->resize(static_cast<size_t>(total_chunks) * 32);
       HIP_CHECK(hipMemcpy(&(*leaves_out)[0], dleaves.get(), leaves_out->size(),
                           hipMemcpyDeviceToHost));
@@ -482,6 +495,7 @@ class GpuEngine {
     stats["bytes"] = size;
     stats["gib_per_s"] = size / (t1 - t0) / (1 << 30);
     stats["net_conn_seconds"] = net_ns.load() / 1e9;
+    stats["slot_wait_seconds"] = slot_wait_ns.load() / 1e9;
     return stats;
   }
 
@@ -605,9 +619,11 @@ class GpuEngine {
     if (!conn.send_request(method, u.target(), h, static_cast<int64_t>(size)))
       throw std::runtime_error("push: send_request failed");
     bool sent = true;
-    HIP_CHECK(drain_device(src_ptr, size, [&](const char* p, uint64_t len) {
-      return sent = conn.send_body(p, len);
-    }));
+    double slot_wait = 0;
+    HIP_CHECK(drain_device(
+        src_ptr, size,
+        [&](const char* p, uint64_t len) { return sent = conn.send_body(p, len); },
+        &slot_wait));
     if (!sent) throw std::runtime_error("push: send_body failed");
     int status = 0;
     http::Headers rh;
@@ -624,6 +640,7 @@ class GpuEngine {
     stats["seconds"] = t1 - t0;
     stats["bytes"] = size;
     stats["status"] = status;
+    stats["slot_wait_seconds"] = slot_wait;
     return stats;
   }
 
@@ -1343,9 +1360,12 @@ class GpuEngine {
   }
 
  private:
-  Slot* acquire_slot() {
+  // *waited, when given, receives the seconds this call spent blocked.
+  Slot* acquire_slot(double* waited = nullptr) {
     std::unique_lock<std::mutex> lk(mu_);
+    double t0 = now_s();
     cv_free_.wait(lk, [&] { return !free_.empty(); });
+    if (waited) *waited = now_s() - t0;
     Slot* s = free_.front();
     free_.pop();
     return s;
@@ -1358,77 +1378,100 @@ class GpuEngine {
     cv_free_.notify_all();
   }
 
-  // The two pinned slots of a double-buffered D2H drain. Both are taken in
-  // ONE wait: sequential acquire_slot() would hold-and-wait and can deadlock
-  // when >= num_slots drains run concurrently. The destructor waits out any
-  // copy still in flight into a slot before the pool can hand it out again.
+  // The ONE pinned slot of a D2H drain, double-buffered between its two
+  // halves: the second half starts at slot_bytes / 2 rounded down to 4 KiB,
+  // and both halves hold piece_bytes(). A slot below 8 KiB has no halves and
+  // is drained single-buffered as a whole. The slot is taken by the same
+  // single-slot wait the pulls use, so every ring user is a one-slot taker:
+  // NO code path waits for a slot while holding one, and no taker can be
+  // starved by others that need fewer slots at once. The destructor waits
+  // out any copy still in flight into the slot before the pool can hand it
+  // out again.
   class SlotLease {
    public:
-    explicit SlotLease(GpuEngine& eng) : eng_(eng) {
-      std::unique_lock<std::mutex> lk(eng_.mu_);
-      eng_.cv_free_.wait(lk, [&] { return eng_.free_.size() >= 2; });
-      for (Slot*& s : slot_) {
-        s = eng_.free_.front();
-        eng_.free_.pop();
+    SlotLease(GpuEngine& eng, double* waited) : eng_(eng), slot_(eng.acquire_slot(waited)) {
+      size_t half = (eng_.slot_bytes_ / 2) & ~static_cast<size_t>(4095);
+      if (eng_.slot_bytes_ >= 8192) {
+        buffers_ = 2;
+        piece_bytes_ = half;
+        off_[1] = half;
+      } else {
+        buffers_ = 1;
+        piece_bytes_ = eng_.slot_bytes_;
       }
     }
     SlotLease(const SlotLease&) = delete;
     ~SlotLease() {
-      for (int i = 0; i < 2; i++)
-        if (in_flight_[i]) (void)hipEventSynchronize(slot_[i]->event);
-      {
-        std::lock_guard<std::mutex> lk(eng_.mu_);
-        for (Slot* s : slot_) eng_.free_.push(s);
-      }
-      eng_.cv_free_.notify_all();
+      for (int i = 0; i < buffers_; i++)
+        if (in_flight_[i]) (void)hipEventSynchronize(event(i));
+      eng_.release_slot(slot_);
     }
-    const char* host(int i) const { return slot_[i]->host; }
-    // async D2H into slot i on st, then record the slot's event
+    int buffers() const { return buffers_; }
+    uint64_t piece_bytes() const { return piece_bytes_; }
+    const char* host(int i) const { return slot_->host + off_[i]; }
+    // async D2H of len <= piece_bytes() into buffer i on st, then record the
+    // buffer's event
     hipError_t fill(int i, const char* src, uint64_t len, hipStream_t st) {
-      hipError_t e = hipMemcpyAsync(slot_[i]->host, src, len, hipMemcpyDeviceToHost, st);
-      if (e == hipSuccess) e = hipEventRecord(slot_[i]->event, st);
+      hipError_t e =
+          hipMemcpyAsync(slot_->host + off_[i], src, len, hipMemcpyDeviceToHost, st);
+      if (e == hipSuccess) e = hipEventRecord(event(i), st);
       if (e == hipSuccess) in_flight_[i] = true;
       return e;
     }
     hipError_t wait(int i) {
       in_flight_[i] = false;
-      return hipEventSynchronize(slot_[i]->event);
+      return hipEventSynchronize(event(i));
     }
 
    private:
+    hipEvent_t event(int i) const { return i ? slot_->event2 : slot_->event; }
     GpuEngine& eng_;
-    Slot* slot_[2];
+    Slot* slot_;
+    int buffers_;
+    uint64_t piece_bytes_;
+    size_t off_[2] = {0, 0};
     bool in_flight_[2] = {false, false};
   };
 
-  // Stream [src_ptr, src_ptr+size) D2H through two leased pinned slots and
+  // Stream [src_ptr, src_ptr+size) D2H through one leased pinned slot and
   // hand each filled (host_ptr, len) to `consume` in order, the copy into
-  // one slot overlapping the consumer's work on the other. `consume`
-  // returning false stops the drain; a HIP error stops it and is returned.
+  // one half of the slot overlapping the consumer's work on the other (a
+  // D2H fill takes a fraction of what a socket or a SHA-NI chain needs for
+  // the same bytes, so half a slot of lookahead keeps the consumer fed).
+  // `consume` returning false stops the drain; a HIP error stops it and is
+  // returned. *slot_wait, when given, receives the seconds spent blocked
+  // for the slot.
   template <class Consume>
-  hipError_t drain_device(uintptr_t src_ptr, uint64_t size, Consume&& consume) {
+  hipError_t drain_device(uintptr_t src_ptr, uint64_t size, Consume&& consume,
+                          double* slot_wait = nullptr) {
     if (!size) return hipSuccess;
     const char* src = reinterpret_cast<const char*>(src_ptr);
     // streams chosen round-robin so concurrent drains (part uploads, blob
     // digests) don't serialize on one stream
     hipStream_t st_a = streams_[push_rr_.fetch_add(1) % streams_.size()];
     hipStream_t st_b = streams_[push_rr_.fetch_add(1) % streams_.size()];
-    SlotLease lease(*this);
-    int cur = 0, nxt = 1;
+    SlotLease lease(*this, slot_wait);
+    const uint64_t piece = lease.piece_bytes();
+    const bool lookahead = lease.buffers() == 2;
+    int cur = 0;
     uint64_t off = 0;
-    uint64_t cur_len = std::min<uint64_t>(slot_bytes_, size);
+    uint64_t cur_len = std::min<uint64_t>(piece, size);
     hipError_t e = lease.fill(cur, src, cur_len, st_a);
     while (e == hipSuccess && off < size) {
       uint64_t next_off = off + cur_len;
-      uint64_t next_len = next_off < size ? std::min<uint64_t>(slot_bytes_, size - next_off) : 0;
-      if (next_len) {
+      uint64_t next_len = next_off < size ? std::min<uint64_t>(piece, size - next_off) : 0;
+      int nxt = lookahead ? cur ^ 1 : cur;
+      if (next_len && lookahead) {
         e = lease.fill(nxt, src + next_off, next_len, st_b);
         if (e != hipSuccess) break;
         std::swap(st_a, st_b);
       }
       e = lease.wait(cur);
       if (e != hipSuccess || !consume(lease.host(cur), cur_len)) break;
-      std::swap(cur, nxt);
+      // single-buffered: the next piece may only overwrite the buffer once
+      // the consumer is done with it
+      if (next_len && !lookahead) e = lease.fill(nxt, src + next_off, next_len, st_a);
+      cur = nxt;
       off = next_off;
       cur_len = next_len;
     }
@@ -1523,6 +1566,7 @@ class GpuEngine {
   int device_;
   size_t slot_bytes_;
   std::atomic<int> push_rr_{0};
+  std::atomic<int> hash_rr_{0};  // stream of the next pull's hash launch
   std::vector<Slot> slots_;
   std::queue<Slot*> free_;
   std::deque<Slot*> pending_;

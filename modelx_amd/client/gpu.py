@@ -4,9 +4,9 @@ Orchestrates the native pinned-ring engine (modelx_amd._core, built from
 core/src/engine.cpp + core/hip/sha256.hip):
 
 - ``pull_to_gpu``: manifest → presigned URL per blob → parallel ranged GETs
-  into pinned slots → hipMemcpyAsync onto the device buffer → CDNA4 SHA-256
-  chunk kernel verifies the chunked digest. Returns ``dict[name,
-  torch.Tensor]`` (uint8) resident in HBM.
+  into pinned slots → hipMemcpyAsync onto the device buffer → one launch of
+  the CDNA4 SHA-256 chunk kernel over the landed blob verifies the chunked
+  digest. Returns ``dict[name, torch.Tensor]`` (uint8) resident in HBM.
 - ``push_from_gpu``: chunk-digest the device buffers on GPU, presigned
   (multi)part upload streamed D2H through the pinned ring, manifest PUT last.
 - multi-GPU fan-out: rank 0 pulls, RCCL broadcast over xGMI per pipeline
@@ -560,9 +560,10 @@ class GpuClient:
 
     def _land_transfer(self, job: _Landing) -> "torch.Tensor":
         """Full transfer, then verify. Where the slots cover whole chunks the
-        chunks are hashed on each slot's stream right behind its H2D copy,
-        so verification overlaps the transfer; a streamed root that misses
-        the digest goes on to the full verify and the chunk refetch."""
+        engine hashes the landed blob itself, in one launch once the last
+        copy has ended, and returns the leaves with the transfer; a root
+        that misses the digest goes on to the full verify and the chunk
+        refetch."""
         desc, cs = job.desc, job.cs
         target = rules.chunked_target(desc)
         t0 = time.monotonic()
