@@ -10,6 +10,7 @@
 
 #include <cstdint>
 
+#include "modelx/aead_core.hpp"
 #include "modelx/crc32c_core.hpp"
 #include "modelx/tar_core.hpp"
 #include "modelx/zstd_host.hpp"
@@ -94,6 +95,23 @@ struct DedupRange {
   uint64_t len;
 };
 
+// One launch of modelx_aead_segments (core/hip/aead.hip): seal (open == 0) or
+// open the n bytes at the device address src into dst, cut into nseg ==
+// aead::segment_count(n, seg_bytes) segments (modelx/aead_core.hpp), with tag
+// i at tags + 16 * i. dst is 16 B aligned; src may equal dst and may otherwise
+// have any alignment; tags may have any alignment.
+struct AeadJob {
+  aead::Key key;
+  uint64_t src;
+  uint64_t dst;
+  uint64_t tags;
+  uint64_t n;
+  uint64_t seg_bytes;
+  uint64_t nseg;
+  uint32_t open;
+  uint32_t pad_;
+};
+
 }  // namespace abi
 }  // namespace modelx
 
@@ -173,5 +191,12 @@ hipError_t modelx_byte_planes(const void* src, void* dst, uint64_t size, uint32_
 hipError_t modelx_crc32c_ranges(const modelx::abi::CrcRange* ranges_dev, uint32_t nranges,
                                 uint32_t total_segments, uint32_t* seg_vals_dev,
                                 uint32_t* out_dev, hipStream_t stream);
+// ChaCha20-Poly1305 over every segment of `job`. Seal writes the ciphertext
+// and the tags. Open writes the plaintext, compares every tag and leaves in
+// *bad_dev (which the caller sets to 0xFFFFFFFF) the lowest segment index
+// whose tag differs. hipErrorInvalidValue for a job that breaks AeadJob's
+// rules. Reads no byte outside [src, src + n) and the tags.
+hipError_t modelx_aead_segments(modelx::abi::AeadJob job, uint32_t* bad_dev,
+                                hipStream_t stream);
 
 }  // extern "C"

@@ -59,6 +59,7 @@
 namespace py = pybind11;
 using namespace modelx;
 using modelx::abi::ChunkLeavesDesc;
+using modelx::abi::AeadJob;
 using modelx::abi::CopySeg;
 using modelx::abi::CrcRange;
 using modelx::abi::DedupRange;
@@ -116,6 +117,44 @@ void check_cdc_bits(const char* who, uint64_t bits) {
   if (!cdc::valid_bits(bits))
     throw std::invalid_argument(std::string(who) + ": UNSUPPORTED cdc bits " +
                                 std::to_string(bits) + " (1..24)");
+}
+
+// The checks every AEAD entry point makes before it touches a byte: a 32-byte
+// key, a segment size aead_core.hpp accepts, at least one byte, and a segment
+// count the kernel's 32-bit mismatch index can hold.
+aead::Key checked_aead_key(const char* who, const py::bytes& key32, uint64_t n, uint64_t seg) {
+  std::string_view k = key32;
+  if (k.size() != aead::kKeyBytes)
+    throw std::invalid_argument(std::string(who) + ": the key is " + std::to_string(k.size()) +
+                                " bytes, not 32");
+  if (!aead::valid_segment(seg))
+    throw std::invalid_argument(std::string(who) + ": UNSUPPORTED segment size " +
+                                std::to_string(seg) +
+                                " (a multiple of 1024 from 1024 to 16 MiB)");
+  if (n == 0) throw std::invalid_argument(std::string(who) + ": nothing to seal (n == 0)");
+  if (n > (uint64_t(1) << 62) || aead::segment_count(n, seg) >= UINT32_MAX)
+    throw std::invalid_argument(std::string(who) + ": " + std::to_string(n) +
+                                " bytes are too many segments of " + std::to_string(seg));
+  return aead::key_from_bytes(reinterpret_cast<const uint8_t*>(k.data()));
+}
+
+AeadJob aead_job(const char* who, const py::bytes& key32, uintptr_t src, uint64_t n,
+                      uintptr_t dst, uint64_t seg, bool open) {
+  AeadJob job{};
+  job.key = checked_aead_key(who, key32, n, seg);
+  const uint64_t total = aead::sealed_size(n, seg);
+  if (src == 0 || dst == 0 || src > UINTPTR_MAX - n || dst > UINTPTR_MAX - total)
+    throw std::runtime_error(std::string(who) + ": null pointer or a range that wraps");
+  if (dst & 15u)
+    throw std::runtime_error(std::string(who) + ": destination is not 16-byte aligned");
+  job.src = src;
+  job.dst = dst;
+  job.tags = dst + n;
+  job.n = n;
+  job.seg_bytes = seg;
+  job.nseg = aead::segment_count(n, seg);
+  job.open = open ? 1 : 0;
+  return job;
 }
 
 py::list ranges_to_py(const std::vector<std::pair<uint64_t, uint64_t>>& ranges) {
@@ -826,6 +865,47 @@ class GpuEngine {
     HIP_CHECK(hipStreamSynchronize(hash_stream_));
     HIP_CHECK(hipMemcpy(out.data(), dout, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
     return out;
+  }
+
+  // ------------------------------------------------------------- aead ----
+
+  // ChaCha20-Poly1305 of device memory (core/hip/aead.hip; layout and
+  // arithmetic are aead_core.hpp's). aead_seal writes the sealed blob of the n
+  // bytes at src_ptr, n + 16 * nseg bytes, at dst_ptr (16 B aligned; equal to
+  // src_ptr or disjoint from the source). aead_open opens the sealed blob of
+  // stored_size bytes at ptr in place, so that the plaintext is its first n
+  // bytes, and returns the first segment whose tag does not match, or -1; the
+  // bytes of a blob that does not return -1 must not be used. Both run on
+  // hash_stream_ and return after it has synchronised.
+  void aead_seal(const py::bytes& key32, uintptr_t src_ptr, uint64_t n, uintptr_t dst_ptr,
+                 uint64_t seg) {
+    AeadJob job = aead_job("aead_seal", key32, src_ptr, n, dst_ptr, seg, false);
+    const uint64_t total = aead::sealed_size(n, seg);
+    if (src_ptr != dst_ptr && src_ptr < dst_ptr + total && dst_ptr < src_ptr + n)
+      throw std::runtime_error("aead_seal: source and destination overlap");
+    HIP_CHECK(hipSetDevice(device_));
+    py::gil_scoped_release release;
+    HIP_CHECK(modelx_aead_segments(job, nullptr, hash_stream_));
+    HIP_CHECK(hipStreamSynchronize(hash_stream_));
+  }
+
+  int64_t aead_open(const py::bytes& key32, uintptr_t ptr, uint64_t stored_size, uint64_t n,
+                    uint64_t seg) {
+    AeadJob job = aead_job("aead_open", key32, ptr, n, ptr, seg, true);
+    if (stored_size != aead::sealed_size(n, seg))
+      throw std::runtime_error("aead_open: " + std::to_string(stored_size) +
+                               " stored bytes are not the sealed size of " + std::to_string(n) +
+                               " bytes at segment " + std::to_string(seg));
+    HIP_CHECK(hipSetDevice(device_));
+    py::gil_scoped_release release;
+    std::lock_guard<std::mutex> lk(aead_mu_);
+    uint32_t* dbad = aead_bad_.reserve<uint32_t>(sizeof(uint32_t));
+    uint32_t bad = UINT32_MAX;
+    HIP_CHECK(hipMemcpyAsync(dbad, &bad, sizeof bad, hipMemcpyHostToDevice, hash_stream_));
+    HIP_CHECK(modelx_aead_segments(job, dbad, hash_stream_));
+    HIP_CHECK(hipStreamSynchronize(hash_stream_));
+    HIP_CHECK(hipMemcpy(&bad, dbad, sizeof bad, hipMemcpyDeviceToHost));
+    return bad == UINT32_MAX ? -1 : static_cast<int64_t>(bad);
   }
 
   // ------------------------------------------------------ byte planes ----
@@ -1591,6 +1671,8 @@ class GpuEngine {
   DeviceScratch ds_leaves_, ds_addr_, ds_len_;
   std::mutex crc_mu_;  // guards the crc32c_ranges scratch below
   DeviceScratch cs_descs_, cs_segs_, cs_out_;
+  std::mutex aead_mu_;  // guards aead_open's mismatch word
+  DeviceScratch aead_bad_;
   std::mutex cdc_mu_;  // guards the candidate kernel's scratch below
   DeviceScratch cd_counts_, cd_lists_;
 };
@@ -1667,6 +1749,12 @@ PYBIND11_MODULE(_core, m) {
            py::arg("literals_only") = false)
       .def("byte_planes", &GpuEngine::byte_planes, py::arg("items"), py::arg("merge"))
       .def("crc32c_ranges", &GpuEngine::crc32c_ranges, py::arg("ranges"))
+      .def("aead_seal", &GpuEngine::aead_seal, py::arg("key32"), py::arg("src_ptr"),
+           py::arg("n"), py::arg("dst_ptr"),
+           py::arg("seg") = (uint64_t)aead::kDefaultSegmentBytes)
+      .def("aead_open", &GpuEngine::aead_open, py::arg("key32"), py::arg("ptr"),
+           py::arg("stored_size"), py::arg("n"),
+           py::arg("seg") = (uint64_t)aead::kDefaultSegmentBytes)
       .def("zstd_decompress_device", &GpuEngine::zstd_decompress_device, py::arg("src_ptr"),
            py::arg("src_len"), py::arg("dst_ptr"), py::arg("dst_cap"))
       .def("synchronize", &GpuEngine::synchronize);
@@ -1766,6 +1854,51 @@ PYBIND11_MODULE(_core, m) {
   m.def("crc32c_combine", &crc32c::combine, py::arg("crc_a"), py::arg("crc_b"),
         py::arg("len_b"));
   m.attr("CRC32C_SEGMENT_BYTES") = modelx::abi::kCrc32cSegmentBytes;
+  // ChaCha20-Poly1305 sealed blobs on host bytes (aead_core.hpp): the model of
+  // GpuEngine::aead_seal / aead_open and the CPU client's path. aead_open_host
+  // returns the n plaintext bytes, or raises ValueError naming the first
+  // segment whose tag does not match.
+  m.def(
+      "aead_seal_host",
+      [](py::bytes key32, py::bytes data, uint64_t seg) {
+        std::string_view s = data;
+        aead::Key key = checked_aead_key("aead_seal_host", key32, s.size(), seg);
+        std::string out(aead::sealed_size(s.size(), seg), '\0');
+        {
+          py::gil_scoped_release release;
+          aead::seal_blob(key, reinterpret_cast<const uint8_t*>(s.data()), s.size(), seg,
+                          reinterpret_cast<uint8_t*>(&out[0]));
+        }
+        return py::bytes(out);
+      },
+      py::arg("key32"), py::arg("data"),
+      py::arg("seg") = (uint64_t)aead::kDefaultSegmentBytes);
+  m.def(
+      "aead_open_host",
+      [](py::bytes key32, py::bytes stored, uint64_t n, uint64_t seg) {
+        std::string_view s = stored;
+        aead::Key key = checked_aead_key("aead_open_host", key32, n, seg);
+        if (s.size() != aead::sealed_size(n, seg))
+          throw std::invalid_argument("aead_open_host: " + std::to_string(s.size()) +
+                                      " stored bytes are not the sealed size of " +
+                                      std::to_string(n) + " bytes at segment " +
+                                      std::to_string(seg));
+        std::string out(n, '\0');
+        int64_t bad;
+        {
+          py::gil_scoped_release release;
+          bad = aead::open_blob(key, reinterpret_cast<const uint8_t*>(s.data()), n, seg,
+                                reinterpret_cast<uint8_t*>(&out[0]));
+        }
+        if (bad >= 0)
+          throw std::invalid_argument("aead_open_host: tag mismatch in segment " +
+                                      std::to_string(bad));
+        return py::bytes(out);
+      },
+      py::arg("key32"), py::arg("stored"), py::arg("n"),
+      py::arg("seg") = (uint64_t)aead::kDefaultSegmentBytes);
+  m.attr("AEAD_DEFAULT_SEGMENT_BYTES") = (uint64_t)aead::kDefaultSegmentBytes;
+  m.attr("AEAD_ROW_BYTES") = (uint64_t)aead::kRowBytes;
   // Content-defined chunking on host bytes (cdc_core.hpp): the model of
   // GpuEngine::cdc_candidates / cdc_chunks, and their overflow path.
   m.def(

@@ -33,8 +33,11 @@ class Client:
                                 compress=compress, planes=planes)
 
     def pull(self, repository: str, version: str, into_dir: str,
-             quiet: Optional[bool] = None) -> types.Manifest:
-        return self.puller.pull(repository, version or "latest", into_dir, quiet=quiet)
+             quiet: Optional[bool] = None, key: Optional[bytes] = None) -> types.Manifest:
+        """``key``: the 32-byte key of blobs pushed with ``encrypt=True``."""
+        if key is None:
+            return self.puller.pull(repository, version or "latest", into_dir, quiet=quiet)
+        return self.puller.pull(repository, version or "latest", into_dir, quiet=quiet, key=key)
 
     def get_manifest(self, repository: str, version: str = "") -> types.Manifest:
         return self.remote.get_manifest(repository, version)

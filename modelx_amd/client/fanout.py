@@ -22,6 +22,7 @@ from dataclasses import dataclass, field
 from typing import Callable, Dict, List, Optional, Sequence, Tuple
 
 from ..wire import types
+from . import gpu_rules as rules
 from .gpu_rules import payload_descriptors
 
 DEFAULT_PIPELINE_CHUNK = 256 << 20
@@ -103,6 +104,7 @@ def fanout_pull_broadcast(dist, gpu_client, repository: str, version: str,
     rank = dist.get_rank()
     manifest = gpu_client.remote.get_manifest(repository, version)
     out = {}
+    rules.refuse_sealed(manifest.blobs, "fanout_pull_broadcast")
     for desc in payload_descriptors(manifest, skip_sidecars):
         tensor = torch.empty(desc.size, dtype=torch.uint8, device=dev)
         fetch = None
@@ -153,6 +155,7 @@ def fanout_pull_sharded(dist, gpu_client, repository: str, version: str, device:
     manifest = gpu_client.remote.get_manifest(repository, version)
     descs = [d for d in manifest.blobs
              if d.size > 0 and d.media_type not in types.SIDECAR_MEDIA_TYPES]
+    rules.refuse_sealed(descs, "fanout_pull_sharded")
     plan = ShardPlan.build(descs, world)
     out = {}
     owned = [d for d in descs if plan.owners[d.name] == rank]

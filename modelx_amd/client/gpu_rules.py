@@ -252,6 +252,96 @@ def part_checksum_headers(crc: int) -> Dict[str, str]:
     return {PART_CHECKSUM_HEADER: base64.b64encode(crc.to_bytes(4, "big")).decode()}
 
 
+# ---- client-side encryption (core/include/modelx/aead_core.hpp) ------------
+
+_BLOB_KEY_LABEL = b"modelx-aead-v1\0"
+
+
+def check_encrypt_key(key) -> None:
+    """The ``key`` option of the clients: ``None`` or 32 bytes; anything
+    else is UNSUPPORTED."""
+    if key is not None and not (isinstance(key, (bytes, bytearray)) and len(key) == 32):
+        raise er.ModelxError(er.ErrCode.UNSUPPORTED,
+                             "the encryption key must be 32 bytes (or None)")
+
+
+def encrypt_segment(seg) -> int:
+    """The ``encrypt_segment`` option of a push: ``None`` (the default) or a
+    multiple of 1024 from 1024 to 16 MiB; anything else is UNSUPPORTED."""
+    if seg is None:
+        return types.ENCRYPTION_DEFAULT_SEGMENT
+    if not types.encryption_segment_ok(seg):
+        raise er.ModelxError(er.ErrCode.UNSUPPORTED,
+                             f"unsupported encrypt_segment {seg!r}: need a multiple of "
+                             "1024 from 1024 to 16 MiB")
+    return seg
+
+
+def sealed_size(n: int, seg: int) -> int:
+    """Stored size of ``n`` sealed bytes: one 16-byte tag per segment."""
+    return types.sealed_size(n, seg)
+
+
+def blob_key(key: bytes, salt: bytes, seg: int, n: int) -> bytes:
+    """The key one blob is sealed under. It binds the salt, the segment size
+    and the length, so an annotation that was tampered with derives another
+    key and every tag fails. The engine never sees the user's key."""
+    import hashlib
+    import hmac
+
+    return hmac.new(bytes(key), _BLOB_KEY_LABEL + salt + struct.pack("<IQ", seg, n),
+                    hashlib.sha256).digest()
+
+
+def encryption_note(seg: int, n: int, salt: bytes) -> Dict[str, str]:
+    """The annotation a sealed blob's descriptor carries."""
+    return {types.ANNOTATION_ENCRYPTION: types.format_encryption(seg, n, salt)}
+
+
+def encryption(desc: types.Descriptor) -> Optional[tuple]:
+    """``(seg, n, salt)`` of a sealed blob or None; a malformed annotation,
+    or one that does not fit the descriptor's size, raises UNSUPPORTED
+    (``types.parse_encryption``)."""
+    return types.parse_encryption(desc.annotations.get(types.ANNOTATION_ENCRYPTION), desc.size)
+
+
+def opening_key(desc: types.Descriptor, key, what: str = "pull") -> Optional[tuple]:
+    """``(blob key, seg, n)`` to open ``desc`` with, None for a blob that is
+    not sealed. A sealed blob without a key is UNSUPPORTED: its stored bytes
+    are never returned as content."""
+    enc = encryption(desc)
+    if enc is None:
+        return None
+    if key is None:
+        raise er.ModelxError(er.ErrCode.UNSUPPORTED,
+                             f"{what}: blob {desc.name} is encrypted and no key was given")
+    seg, n, salt = enc
+    return blob_key(key, salt, seg, n), seg, n
+
+
+def dedup_allowed(desc: types.Descriptor) -> bool:
+    """Whether a landed blob may be registered in, or gathered from, the
+    chunk-dedup table. A sealed blob may not: it is opened in place, which
+    would rewrite chunks the table holds as resident."""
+    return not desc.annotations.get(types.ANNOTATION_ENCRYPTION)
+
+
+def refuse_sealed(descs, what: str) -> None:
+    """UNSUPPORTED when any of ``descs`` is sealed: for paths that move
+    stored bytes between devices and have no step that opens them."""
+    for desc in descs:
+        if desc.annotations.get(types.ANNOTATION_ENCRYPTION):
+            raise er.ModelxError(er.ErrCode.UNSUPPORTED,
+                                 f"{what}: blob {desc.name} is encrypted; pull it with "
+                                 "GpuClient(key=...).pull_to_gpu")
+
+
+def bad_tag(desc: types.Descriptor, segment: int) -> er.ModelxError:
+    return er.ModelxError(er.ErrCode.DIGEST_INVALID,
+                          f"authentication failed for {desc.name}: tag mismatch in "
+                          f"segment {segment} (wrong key or altered blob)")
+
+
 def check_dir_names(tensors, dirs, cdc: bool = False) -> None:
     """Every descriptor name the manifest of a push will carry must be
     unique: the config, each blob and each blob's leaves sidecar (and its

@@ -14,6 +14,7 @@ from ..wire import digest as dg
 from ..wire import errors as er
 from ..wire import types
 from . import extension as ext
+from . import gpu_rules as rules
 from .progress import Bar, MultiBar
 from .push import MODELX_CACHE_DIR, PULL_PUSH_CONCURRENCY
 
@@ -37,7 +38,12 @@ class Puller:
         self.concurrency = concurrency
 
     def pull(self, repository: str, version: str, into_dir: str,
-             blob_filter=None, quiet: Optional[bool] = None) -> types.Manifest:
+             blob_filter=None, quiet: Optional[bool] = None,
+             key: Optional[bytes] = None) -> types.Manifest:
+        """``key`` (32 bytes) opens blobs that were pushed sealed
+        (``modelx.amd/encryption``); without it such a blob is UNSUPPORTED
+        and nothing of it is written."""
+        rules.check_encrypt_key(key)
         os.makedirs(into_dir, exist_ok=True)
         # one round trip for manifest + presigned locations where the
         # server supports pull plans (falls back transparently)
@@ -55,23 +61,32 @@ class Puller:
         descs: List[types.Descriptor] = [manifest.config] + list(manifest.blobs)
         if blob_filter is not None:
             descs = [d for d in descs if blob_filter(d)]
-        self.pull_blobs(repository, descs, into_dir, quiet=quiet,
-                        plan_blobs=plan_blobs)
+        if key is None:
+            self.pull_blobs(repository, descs, into_dir, quiet=quiet,
+                            plan_blobs=plan_blobs)
+        else:
+            self.pull_blobs(repository, descs, into_dir, quiet=quiet,
+                            plan_blobs=plan_blobs, key=key)
         return manifest
 
     def pull_blobs(self, repository: str, descs: List[types.Descriptor], into_dir: str,
-                   quiet: Optional[bool] = None, plan_blobs: Optional[dict] = None) -> None:
+                   quiet: Optional[bool] = None, plan_blobs: Optional[dict] = None,
+                   key: Optional[bytes] = None) -> None:
         # the pull plan is threaded through as a parameter (not instance
         # state) so concurrent pull() calls on one Puller can't cross plans
         with MultiBar("pull", self.concurrency, quiet=quiet) as mb:
             for desc in descs:
                 mb.go(desc.name, desc.size,
                       lambda bar, d=desc: self._pull_one(repository, d, into_dir, bar,
-                                                         plan_blobs))
+                                                         plan_blobs, key))
             mb.wait()
 
     def _pull_one(self, repository: str, desc: types.Descriptor, into_dir: str,
-                  bar: Optional[Bar], plan_blobs: Optional[dict] = None) -> None:
+                  bar: Optional[Bar], plan_blobs: Optional[dict] = None,
+                  key: Optional[bytes] = None) -> None:
+        opening = rules.opening_key(desc, key)
+        if opening:
+            return self._pull_sealed_file(repository, desc, into_dir, bar, plan_blobs, opening)
         if desc.media_type in (types.MEDIA_TYPE_MODEL_DIRECTORY_TARGZ,
                                types.MEDIA_TYPE_MODEL_DIRECTORY_TAR):
             self._pull_directory(repository, desc, into_dir, bar, plan_blobs)
@@ -94,6 +109,51 @@ class Puller:
                 bar.set_status("up to date", complete=True)
             return
         self.pull_blob(repository, desc, dest, bar, plan_blobs=plan_blobs)
+        if desc.mode:
+            os.chmod(dest, desc.mode & 0o7777)
+
+    def _pull_sealed_file(self, repository: str, desc: types.Descriptor, into_dir: str,
+                          bar: Optional[Bar], plan_blobs: Optional[dict], opening) -> None:
+        """CPU pull of a sealed file blob (GPU path: GpuClient._open_landed):
+        the stored bytes are fetched into the cache and verified against
+        desc.digest by pull_blob, opened with the host model
+        (``_core.aead_open_host``), and the plaintext then takes the zstd and
+        byte-plane steps of an unsealed blob. A tag that does not match is
+        DIGEST_INVALID and nothing is written."""
+        from modelx_amd import _core
+
+        if desc.media_type not in (types.MEDIA_TYPE_MODEL_FILE,
+                                   types.MEDIA_TYPE_MODEL_FILE_ZSTD):
+            raise er.ModelxError(er.ErrCode.UNSUPPORTED,
+                                 f"encrypted blob {desc.name} has media type {desc.media_type}")
+        zstd = desc.media_type == types.MEDIA_TYPE_MODEL_FILE_ZSTD
+        planes = types.parse_byte_planes(desc.annotations.get(types.ANNOTATION_BYTE_PLANES))
+        blob_key, seg, n = opening
+        dest = os.path.join(into_dir, desc.name)
+        cache_dir = os.path.join(into_dir, MODELX_CACHE_DIR)
+        os.makedirs(cache_dir, exist_ok=True)
+        sealed_path = os.path.join(cache_dir, desc.name + ".sealed")
+        self.pull_blob(repository, desc, sealed_path, bar, plan_blobs=plan_blobs)
+        with open(sealed_path, "rb") as f:
+            stored = f.read()
+        os.remove(sealed_path)
+        try:
+            raw = _core.aead_open_host(blob_key, stored, n, seg)
+        except ValueError as e:
+            raise er.ModelxError(er.ErrCode.DIGEST_INVALID,
+                                 f"authentication failed for {desc.name}: {e} "
+                                 "(wrong key or altered blob)") from e
+        if zstd:
+            raw = _core.zstd_decompress_cpu(raw)
+            if planes:
+                raw = _core.byte_planes_cpu(raw, planes[0], planes[1], True)
+            raw_digest = desc.annotations.get(types.ANNOTATION_RAW_DIGEST, "")
+            if raw_digest and not dg.verify_bytes(raw, raw_digest):
+                raise ValueError(f"uncompressed digest mismatch for {desc.name}")
+        tmp = dest + ".part"
+        with open(tmp, "wb") as f:
+            f.write(raw)
+        os.replace(tmp, dest)
         if desc.mode:
             os.chmod(dest, desc.mode & 0o7777)
 

@@ -107,6 +107,77 @@ def parse_byte_planes(note) -> Optional[tuple]:
         raise bad()
     return elem, group
 
+
+#   client-side encryption: the stored bytes are a sealed blob
+#   (core/include/modelx/aead_core.hpp), "chacha20-poly1305;seg=<dec>;size=<n
+#   dec>;salt=<32 hex>". The n bytes the blob would otherwise have stored are
+#   sealed in segments of `seg` bytes under a key derived from the user's key,
+#   the salt, seg and n; the ciphertext keeps their offsets and one 16-byte tag
+#   per segment follows, so the descriptor's size is n + 16 * ceil(n / seg).
+#   Media type, digest, size and every chunk annotation describe the sealed
+#   bytes; raw-digest on a +zstd blob still describes the plaintext.
+ANNOTATION_ENCRYPTION = "modelx.amd/encryption"
+ENCRYPTION_CIPHER = "chacha20-poly1305"
+ENCRYPTION_DEFAULT_SEGMENT = 128 << 10
+ENCRYPTION_MIN_SEGMENT = 1024
+ENCRYPTION_MAX_SEGMENT = 16 << 20
+ENCRYPTION_TAG_BYTES = 16
+ENCRYPTION_SALT_BYTES = 16
+
+
+def encryption_segment_ok(seg) -> bool:
+    return (isinstance(seg, int) and not isinstance(seg, bool)
+            and ENCRYPTION_MIN_SEGMENT <= seg <= ENCRYPTION_MAX_SEGMENT
+            and seg % ENCRYPTION_MIN_SEGMENT == 0)
+
+
+def sealed_size(n: int, seg: int) -> int:
+    return n + ENCRYPTION_TAG_BYTES * ((n + seg - 1) // seg)
+
+
+def format_encryption(seg: int, n: int, salt: bytes) -> str:
+    return f"{ENCRYPTION_CIPHER};seg={seg};size={n};salt={salt.hex()}"
+
+
+def parse_encryption(note, stored_size: int) -> Optional[tuple]:
+    """``(seg, n, salt)`` from an encryption annotation value on a descriptor
+    of ``stored_size`` bytes, ``None`` when the annotation is absent (``""``
+    or ``None``). A value that is not exactly the format above, a ``seg`` out
+    of range, ``n`` < 1 or a ``stored_size`` that is not the sealed size of
+    ``n`` at ``seg`` raises ``ModelxError(UNSUPPORTED)``: sealed bytes are
+    never handed out as content."""
+    from . import errors as er
+
+    if note is None or (isinstance(note, str) and note == ""):
+        return None
+
+    def bad():
+        return er.ModelxError(er.ErrCode.UNSUPPORTED,
+                              f"unsupported {ANNOTATION_ENCRYPTION} annotation {note!r} "
+                              f"on a blob of {stored_size} bytes")
+
+    if not isinstance(note, str):
+        raise bad()
+    fields = note.split(";")
+    if len(fields) != 4 or fields[0] != ENCRYPTION_CIPHER:
+        raise bad()
+    values = []
+    for field, name in zip(fields[1:], ("seg", "size", "salt")):
+        key, eq, value = field.partition("=")
+        if key != name or not eq or not value.isascii():
+            raise bad()
+        values.append(value)
+    seg_s, n_s, salt_s = values
+    hexdigits = set("0123456789abcdef")
+    if (not seg_s.isdigit() or not n_s.isdigit() or len(seg_s) > 9 or len(n_s) > 19
+            or len(salt_s) != 2 * ENCRYPTION_SALT_BYTES or not set(salt_s) <= hexdigits):
+        raise bad()
+    seg, n = int(seg_s), int(n_s)
+    if not encryption_segment_ok(seg) or n < 1 or stored_size != sealed_size(n, seg):
+        raise bad()
+    return seg, n, bytes.fromhex(salt_s)
+
+
 GO_ZERO_TIME = "0001-01-01T00:00:00Z"
 
 
