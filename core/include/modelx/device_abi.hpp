@@ -12,6 +12,7 @@
 
 #include "modelx/aead_core.hpp"
 #include "modelx/crc32c_core.hpp"
+#include "modelx/deflate_core.hpp"
 #include "modelx/tar_core.hpp"
 #include "modelx/zstd_host.hpp"
 
@@ -112,6 +113,20 @@ struct AeadJob {
   uint32_t pad_;
 };
 
+// One chunk of modelx_deflate_chunks (core/hip/deflate.hip): the bytes the
+// chunk becomes, with deflate::kStoredFlag set when it is stored (its slot is
+// then not written), and the raw CRC-32 of its input bytes.
+struct DeflateChunkOut {
+  uint32_t size;
+  uint32_t crc_raw;
+};
+
+// Workgroups of the chunk kernel (three per CU); each owns
+// deflate::kChunkBytes tokens of scratch. A chunk's slot holds its output
+// image rounded up to 16 B.
+constexpr uint32_t kDeflateMaxBlocks = 768;
+constexpr uint64_t kDeflateSlotStride = deflate::kChunkBytes + 16;
+
 }  // namespace abi
 }  // namespace modelx
 
@@ -198,5 +213,19 @@ hipError_t modelx_crc32c_ranges(const modelx::abi::CrcRange* ranges_dev, uint32_
 // rules. Reads no byte outside [src, src + n) and the tags.
 hipError_t modelx_aead_segments(modelx::abi::AeadJob job, uint32_t* bad_dev,
                                 hipStream_t stream);
+// DEFLATE chunks [first_chunk, first_chunk + nchunks) of the `size` bytes at
+// src (modelx/deflate_core.hpp). token_scratch holds min(nchunks,
+// kDeflateMaxBlocks) * deflate::kChunkBytes 32-bit tokens; slots holds nchunks
+// * kDeflateSlotStride bytes, 16 B aligned; out_dev[i] describes chunk
+// first_chunk + i. Reads no byte outside the 16 B aligned words of the source.
+hipError_t modelx_deflate_chunks(const void* src, uint64_t size, uint64_t first_chunk,
+                                 uint32_t nchunks, void* token_scratch, void* slots,
+                                 modelx::abi::DeflateChunkOut* out_dev, hipStream_t stream);
+// Copies every chunk of such a launch to dst_addr_dev[i] (any alignment): its
+// slot's bytes, or for a stored chunk the block header and the source bytes.
+hipError_t modelx_deflate_gather(const void* src, uint64_t size, uint64_t first_chunk,
+                                 uint32_t nchunks, const void* slots,
+                                 const modelx::abi::DeflateChunkOut* out_dev,
+                                 const uint64_t* dst_addr_dev, hipStream_t stream);
 
 }  // extern "C"

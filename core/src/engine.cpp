@@ -908,6 +908,83 @@ class GpuEngine {
     return bad == UINT32_MAX ? -1 : static_cast<int64_t>(bad);
   }
 
+  // ------------------------------------------------------------- gzip ----
+
+  // Compress the `size` bytes at src_ptr into one gzip member at dst_ptr
+  // (core/hip/deflate.hip; format and host model are deflate_core.hpp's, and
+  // the bytes equal deflate::gzip_compress of the same input). Chunks are
+  // compressed into per-chunk slots in batches, their sizes read back and
+  // prefix-summed, and one gather launch per batch moves them behind the
+  // header; the chunk kernel also leaves each chunk's raw CRC-32, joined here
+  // for the trailer. Runs on hash_stream_ and returns the stored size after it
+  // has synchronised. dst_cap must be at least gzip_compress_bound(size).
+  uint64_t gzip_compress_device(uintptr_t src_ptr, uint64_t size, uintptr_t dst_ptr,
+                                uint64_t dst_cap) {
+    namespace df = modelx::deflate;
+    using modelx::abi::DeflateChunkOut;
+    const uint64_t bound = df::gzip_bound(size);
+    if (dst_cap < bound)
+      throw std::runtime_error("gzip_compress_device: dst_cap " + std::to_string(dst_cap) +
+                               " is below the bound " + std::to_string(bound));
+    if (dst_ptr == 0 || (size && src_ptr == 0) || src_ptr > UINTPTR_MAX - size ||
+        dst_ptr > UINTPTR_MAX - bound)
+      throw std::runtime_error("gzip_compress_device: null or wrapping range");
+    if (size && src_ptr < dst_ptr + bound && dst_ptr < src_ptr + size)
+      throw std::runtime_error("gzip_compress_device: source and destination overlap");
+    HIP_CHECK(hipSetDevice(device_));
+    py::gil_scoped_release release;
+    std::lock_guard<std::mutex> lk(gzip_mu_);
+    const uint64_t nchunks = df::chunk_count(size);
+    std::vector<uint8_t> head(df::kGzipHeader, df::kGzipHeader + df::kGzipHeaderBytes);
+    if (nchunks == 0) {
+      head.resize(df::kGzipHeaderBytes + df::kStoredOverhead);
+      df::stored_header(head.data() + df::kGzipHeaderBytes, 0, true);
+    }
+    uint64_t out = head.size();
+    uint32_t reg = df::crc32::kInit;
+    const uint64_t batch = std::min<uint64_t>(nchunks, 4096);
+    if (batch) {
+      void* dtokens = gz_tokens_.reserve(
+          std::min<uint64_t>(batch, modelx::abi::kDeflateMaxBlocks) * df::kChunkBytes * 4);
+      void* dslots = gz_slots_.reserve(batch * modelx::abi::kDeflateSlotStride);
+      DeflateChunkOut* dout = gz_out_.reserve<DeflateChunkOut>(batch * sizeof(DeflateChunkOut));
+      uint64_t* daddr = gz_addr_.reserve<uint64_t>(batch * sizeof(uint64_t));
+      std::vector<DeflateChunkOut> houts(batch);
+      std::vector<uint64_t> haddr(batch);
+      const void* src = reinterpret_cast<const void*>(src_ptr);
+      for (uint64_t first = 0; first < nchunks; first += batch) {
+        uint32_t n = static_cast<uint32_t>(std::min<uint64_t>(batch, nchunks - first));
+        HIP_CHECK(modelx_deflate_chunks(src, size, first, n, dtokens, dslots, dout, hash_stream_));
+        HIP_CHECK(hipStreamSynchronize(hash_stream_));
+        HIP_CHECK(hipMemcpy(houts.data(), dout, n * sizeof(DeflateChunkOut),
+                            hipMemcpyDeviceToHost));
+        for (uint32_t i = 0; i < n; i++) {
+          uint64_t off = (first + i) * df::kChunkBytes;
+          uint32_t raw_len = static_cast<uint32_t>(std::min<uint64_t>(df::kChunkBytes, size - off));
+          uint32_t stored = houts[i].size & ~df::kStoredFlag;
+          if (stored == 0 || stored > df::chunk_bound(raw_len))
+            throw std::runtime_error("gzip compress kernel: chunk " + std::to_string(first + i) +
+                                     " reports " + std::to_string(stored) + " bytes");
+          haddr[i] = dst_ptr + out;
+          out += stored;
+          reg = df::crc32::mul_xn(reg, raw_len, df::crc32::pow_table()) ^ houts[i].crc_raw;
+        }
+        HIP_CHECK(hipMemcpyAsync(daddr, haddr.data(), n * sizeof(uint64_t), hipMemcpyHostToDevice,
+                                 hash_stream_));
+        HIP_CHECK(modelx_deflate_gather(src, size, first, n, dslots, dout, daddr, hash_stream_));
+        HIP_CHECK(hipStreamSynchronize(hash_stream_));
+      }
+    }
+    uint8_t trailer[df::kGzipTrailerBytes];
+    df::gzip_trailer(trailer, reg ^ df::crc32::kInit, size);
+    HIP_CHECK(hipMemcpyAsync(reinterpret_cast<void*>(dst_ptr), head.data(), head.size(),
+                             hipMemcpyHostToDevice, hash_stream_));
+    HIP_CHECK(hipMemcpyAsync(reinterpret_cast<char*>(dst_ptr) + out, trailer, sizeof trailer,
+                             hipMemcpyHostToDevice, hash_stream_));
+    HIP_CHECK(hipStreamSynchronize(hash_stream_));
+    return out + sizeof trailer;
+  }
+
   // ------------------------------------------------------ byte planes ----
 
   // Byte-plane split (merge=false) or merge (merge=true) of device buffers
@@ -1675,6 +1752,8 @@ class GpuEngine {
   DeviceScratch aead_bad_;
   std::mutex cdc_mu_;  // guards the candidate kernel's scratch below
   DeviceScratch cd_counts_, cd_lists_;
+  std::mutex gzip_mu_;  // guards gzip_compress_device's scratch below
+  DeviceScratch gz_tokens_, gz_slots_, gz_out_, gz_addr_;
 };
 
 bool hip_available() {
@@ -1749,6 +1828,8 @@ PYBIND11_MODULE(_core, m) {
            py::arg("literals_only") = false)
       .def("byte_planes", &GpuEngine::byte_planes, py::arg("items"), py::arg("merge"))
       .def("crc32c_ranges", &GpuEngine::crc32c_ranges, py::arg("ranges"))
+      .def("gzip_compress_device", &GpuEngine::gzip_compress_device, py::arg("src_ptr"),
+           py::arg("size"), py::arg("dst_ptr"), py::arg("dst_cap"))
       .def("aead_seal", &GpuEngine::aead_seal, py::arg("key32"), py::arg("src_ptr"),
            py::arg("n"), py::arg("dst_ptr"),
            py::arg("seg") = (uint64_t)aead::kDefaultSegmentBytes)
@@ -1854,6 +1935,23 @@ PYBIND11_MODULE(_core, m) {
   m.def("crc32c_combine", &crc32c::combine, py::arg("crc_a"), py::arg("crc_b"),
         py::arg("len_b"));
   m.attr("CRC32C_SEGMENT_BYTES") = modelx::abi::kCrc32cSegmentBytes;
+  // gzip of host bytes (deflate_core.hpp): the model that
+  // GpuEngine::gzip_compress_device equals byte for byte.
+  m.def(
+      "gzip_compress_host",
+      [](py::bytes data) {
+        std::string_view s = data;
+        std::vector<uint8_t> out;
+        {
+          py::gil_scoped_release release;
+          out = modelx::deflate::gzip_compress(reinterpret_cast<const uint8_t*>(s.data()),
+                                               s.size());
+        }
+        return py::bytes(reinterpret_cast<const char*>(out.data()), out.size());
+      },
+      py::arg("data"));
+  m.def("gzip_compress_bound", &modelx::deflate::gzip_bound, py::arg("size"));
+  m.attr("GZIP_CHUNK_BYTES") = modelx::deflate::kChunkBytes;
   // ChaCha20-Poly1305 sealed blobs on host bytes (aead_core.hpp): the model of
   // GpuEngine::aead_seal / aead_open and the CPU client's path. aead_open_host
   // returns the n plaintext bytes, or raises ValueError naming the first

@@ -1021,6 +1021,18 @@ class GpuClient:
         self._stat("gpu-tar-pack", total, t0, members=len(members))
         return archive
 
+    def _gzip_on_gpu(self, archive: "torch.Tensor") -> "torch.Tensor":
+        """One gzip member of ``archive``'s bytes (core/hip/deflate.hip), as a
+        view of a buffer of the gzip bound; the caller drops the archive."""
+        size = archive.numel()
+        bound = _core().gzip_compress_bound(size)
+        out = self._device(bound)
+        t0 = time.monotonic()
+        stored = self.engine.gzip_compress_device(archive.data_ptr(), size, out.data_ptr(), bound)
+        chunk = _core().GZIP_CHUNK_BYTES
+        self._stat("push-gzip", size, t0, stored=stored, chunks=(size + chunk - 1) // chunk)
+        return out[:stored]
+
     # -------------------------------------------------------------- push --
 
     def digest_device_blob(self, ptr: int, size: int,
@@ -1275,7 +1287,8 @@ class GpuClient:
                       compress: str = "", digest_mode: str = "chunked",
                       dirs: Optional[Dict[str, Dict[str, "torch.Tensor"]]] = None,
                       planes=0, part_checksum: str = "", cdc=False,
-                      encrypt: bool = False, encrypt_segment=None) -> types.Manifest:
+                      encrypt: bool = False, encrypt_segment=None,
+                      dir_format: str = "tar") -> types.Manifest:
         """Digest on GPU → presigned multipart upload → manifest PUT last.
         With ``compress="zstd"`` each tensor is compressed on-GPU into a
         seekable multi-frame zstd blob (core/hip/zstd.hip) first; the
@@ -1315,6 +1328,22 @@ class GpuClient:
         upload, so until the push returns HBM holds each directory twice: the
         source tensors and their archive.
 
+        ``dir_format`` is ``"tar"`` (the default, described above) or
+        ``"tar+gz"``. With ``"tar+gz"`` each archive, packed exactly as above,
+        is gzipped on the GPU (core/hip/deflate.hip: one gzip member of 32 KiB
+        DEFLATE chunks, the same bytes for the same directory on every push)
+        and pushed as MEDIA_TYPE_MODEL_DIRECTORY_TARGZ, the directory format
+        every client of the original protocol reads. All digests, the leaves
+        sidecar and the part checksums describe the stored ``.gz`` bytes, as
+        in the CPU push; with ``digest_mode="sha256"`` a stock client verifies
+        the blob with no annotation consumed. While a directory is gzipped
+        HBM holds its source tensors, its archive and the gzip bound (the
+        archive plus 5 B per 32 KiB) besides the kernel's scratch (at most
+        224 MiB); the archive is freed once its gzip exists, and the gzip
+        buffer lives until the push returns. Not available with ``cdc``. The
+        kernel's time is the ``push-gzip`` phase of ``last_stats`` (``bytes``
+        the archive, ``stored`` the gzip, ``chunks``).
+
         ``part_checksum`` is ``""`` or ``"crc32c"``. With ``"crc32c"`` every
         presigned upload of the push carries ``x-amz-checksum-crc32c``, so a
         store that verifies it (modelx-s3d, MinIO, AWS) stores only the bytes
@@ -1350,6 +1379,7 @@ class GpuClient:
         ``last_stats``."""
         rules.check_part_checksum(part_checksum)
         cdc_params = rules.cdc_params(cdc)
+        rules.check_dir_format(dir_format, dirs, cdc_params)
         seal_segment = 0
         if encrypt:
             seal_segment = rules.encrypt_segment(encrypt_segment)
@@ -1387,10 +1417,13 @@ class GpuClient:
             tensors = dict(tensors)
             for dname, files in dirs.items():
                 tensors[dname] = self.pack_dir_on_gpu(dname, files)
+                if dir_format == "tar+gz":
+                    tensors[dname] = self._gzip_on_gpu(tensors[dname])
+        dir_media_type = (types.MEDIA_TYPE_MODEL_DIRECTORY_TARGZ if dir_format == "tar+gz"
+                          else types.MEDIA_TYPE_MODEL_DIRECTORY_TAR)
 
         def media_type_of(name: str) -> str:
-            return (types.MEDIA_TYPE_MODEL_DIRECTORY_TAR if name in (dirs or ())
-                    else types.MEDIA_TYPE_MODEL_FILE)
+            return dir_media_type if name in (dirs or ()) else types.MEDIA_TYPE_MODEL_FILE
 
         manifest = types.Manifest(media_type=types.MEDIA_TYPE_MODEL_MANIFEST_JSON)
         now = datetime.now(timezone.utc)

@@ -246,6 +246,24 @@ def check_part_checksum(part_checksum) -> None:
                              "(supported: '' and 'crc32c')")
 
 
+def check_dir_format(dir_format, dirs, cdc) -> None:
+    """The ``dir_format`` option of a GPU push: ``"tar"`` or ``"tar+gz"``.
+    ``"tar+gz"`` needs ``dirs`` and excludes ``cdc``, for the reason ``cdc``
+    excludes ``compress``; anything else is UNSUPPORTED."""
+    if dir_format not in ("tar", "tar+gz"):
+        raise er.ModelxError(er.ErrCode.UNSUPPORTED,
+                             f"unknown dir_format {dir_format!r} "
+                             "(supported: 'tar' and 'tar+gz')")
+    if dir_format == "tar+gz":
+        if not dirs:
+            raise er.ModelxError(er.ErrCode.UNSUPPORTED,
+                                 "dir_format='tar+gz' needs dirs")
+        if cdc:
+            raise er.ModelxError(er.ErrCode.UNSUPPORTED,
+                                 "cdc cannot be combined with dir_format='tar+gz': "
+                                 "chunking compressed bytes finds no shifted content")
+
+
 def part_checksum_headers(crc: int) -> Dict[str, str]:
     """The upload header that carries a CRC-32C value: base64 of its four
     bytes, most significant first, as S3 reads ``x-amz-checksum-crc32c``."""

@@ -24,18 +24,20 @@ SOURCES = [
     "core/hip/crc32c.hip",
     "core/hip/cdc.hip",
     "core/hip/aead.hip",
+    "core/hip/deflate.hip",
     "core/src/zstd_cpu.cpp",
     "core/src/http.cpp",
     "core/src/json.cpp",
 ]
 
-# crc32c.hip, cdc.hip and aead.hip are integer work throughout: keep the
+# crc32c.hip, cdc.hip, aead.hip and deflate.hip are integer work throughout: keep the
 # compiler from forming packed fp32 instructions in them.
 _NO_PACKED_FP32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 EXTRA_FLAGS = {
     "core/hip/crc32c.hip": _NO_PACKED_FP32,
     "core/hip/cdc.hip": _NO_PACKED_FP32,
     "core/hip/aead.hip": _NO_PACKED_FP32,
+    "core/hip/deflate.hip": _NO_PACKED_FP32,
 }
 
 
