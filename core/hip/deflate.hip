@@ -54,6 +54,7 @@
 
 #include "modelx/copy_shifted.hpp"
 #include "modelx/deflate_core.hpp"
+#include "modelx/deflate_wg.hpp"
 #include "modelx/device_abi.hpp"
 
 namespace {
@@ -85,22 +86,8 @@ struct Lds {
 };
 static_assert(sizeof(Lds) <= 64u << 10, "LDS of one workgroup");
 
-struct WgCtx {
-  uint32_t tid;
-  static constexpr uint32_t width = kThreads;
-  __device__ void sync() const { __syncthreads(); }
-  // Call `iter` uses cell iter % 3; thread 0 clears the cell of call iter + 2
-  // behind this call's barrier, after its last readers (call iter - 1) and a
-  // barrier before its next writers.
-  __device__ uint32_t group_max(uint32_t v, uint32_t* cells, uint32_t iter) const {
-    uint32_t* c = cells + iter % 3;
-    if (v) atomicMax(c, v);
-    __syncthreads();
-    uint32_t r = *c;
-    if (tid == 0) cells[(iter + 2) % 3] = 0;
-    return r;
-  }
-};
+using modelx::deflate_wg::WgCtx;  // shared with deflate_lengths.hip, the tests' way in
+static_assert(kThreads == modelx::deflate_wg::kThreads, "deflate_wg.hpp's workgroup");
 
 // Wave 0: tokens of the staged chunk into `tokens`, symbol counts into lds.t.
 __device__ __forceinline__ void parse_wave(Lds& lds, uint32_t n, uint32_t* __restrict__ tokens) {

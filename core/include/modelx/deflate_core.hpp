@@ -234,13 +234,26 @@ struct HostCtx {
   uint32_t group_max(uint32_t v, uint32_t*, uint32_t) const { return v; }
 };
 
+// What one build_lengths call did, for the host's chunk_stats: the Kraft
+// steps it took and how many of them made a code longer.
+struct BuildSteps {
+  uint32_t steps, shrink;
+};
+
 // Code lengths of `nsym` symbols from their counts, at most `maxbits` long.
 // Every thread of the group calls it with the same arguments and gets the
 // same answer; false if the lengths could not be made exact (the caller then
-// stores the chunk). Counts are below 2^16.
+// stores the chunk). Counts are below 2^16. `steps`, if given, is filled on
+// the host; device code ignores it.
 template <class Ctx>
 MX_HD inline bool build_lengths(const Ctx& cx, const uint32_t* hist, uint32_t nsym,
-                                uint32_t maxbits, bool complete, uint8_t* len, uint32_t* cells) {
+                                uint32_t maxbits, bool complete, uint8_t* len, uint32_t* cells,
+                                BuildSteps* steps = nullptr) {
+#if !defined(__HIP_DEVICE_COMPILE__)
+  if (steps) steps->steps = steps->shrink = 0;
+#else
+  (void)steps;
+#endif
   uint32_t total = 0, used = 0, one = 0;
   for (uint32_t s = 0; s < nsym; s++)
     if (hist[s]) total += hist[s], used++, one = s;
@@ -286,6 +299,9 @@ MX_HD inline bool build_lengths(const Ctx& cx, const uint32_t* hist, uint32_t ns
     }
     key = cx.group_max(key, cells, it);
     if (!key) return false;
+#if !defined(__HIP_DEVICE_COMPILE__)
+    if (steps) steps->steps++, steps->shrink += shrink;
+#endif
     uint32_t pick = (key >> 4) & 511u, l = key & 15u;
     if (shrink) K -= 1 << (maxbits - l - 1);
     else K += 1 << (maxbits - l);
@@ -444,11 +460,16 @@ MX_HD inline void stored_header(uint8_t* out, uint32_t n, bool last) {
 
 // All three trees from the lit/len and distance counts, with the header's
 // shape and the block's bit count. Every thread of the group calls it; false
-// if a tree could not be built.
+// if a tree could not be built. `steps`, if given, is three BuildSteps (lit/len,
+// distance, code lengths), filled on the host.
 template <class Ctx>
-MX_HD inline bool build_trees(const Ctx& cx, Trees& t, HeaderShape* shape, uint32_t* block_bits) {
-  if (!build_lengths(cx, t.hist_ll, kNumLL, kLLBits, true, t.len_ll, t.cells)) return false;
-  if (!build_lengths(cx, t.hist_d, kNumD, kLLBits, false, t.len_d, t.cells)) return false;
+MX_HD inline bool build_trees(const Ctx& cx, Trees& t, HeaderShape* shape, uint32_t* block_bits,
+                              BuildSteps* steps = nullptr) {
+  BuildSteps* const st_ll = steps;
+  BuildSteps* const st_d = steps ? steps + 1 : nullptr;
+  BuildSteps* const st_cl = steps ? steps + 2 : nullptr;
+  if (!build_lengths(cx, t.hist_ll, kNumLL, kLLBits, true, t.len_ll, t.cells, st_ll)) return false;
+  if (!build_lengths(cx, t.hist_d, kNumD, kLLBits, false, t.len_d, t.cells, st_d)) return false;
   HeaderShape h = header_shape(t);
   if (cx.tid == 0) {
     assign_codes(t.len_ll, kNumLL, t.code_ll);
@@ -456,7 +477,7 @@ MX_HD inline bool build_trees(const Ctx& cx, Trees& t, HeaderShape* shape, uint3
     count_code_lengths(t, h);
   }
   cx.sync();
-  if (!build_lengths(cx, t.hist_cl, kNumCL, kCLBits, true, t.len_cl, t.cells)) return false;
+  if (!build_lengths(cx, t.hist_cl, kNumCL, kCLBits, true, t.len_cl, t.cells, st_cl)) return false;
   if (cx.tid == 0) assign_codes(t.len_cl, kNumCL, t.code_cl);
   cx.sync();
   h.ncl = trim_hclen(t);
@@ -527,6 +548,68 @@ inline void compress_chunk(const uint8_t* b, uint32_t n, bool last, std::vector<
   uint32_t bytes = write_sync(img.data(), pos, last);
   const uint8_t* p = reinterpret_cast<const uint8_t*>(img.data());  // little-endian words
   out.insert(out.end(), p, p + bytes);
+}
+
+// Which paths compress_chunk takes on one chunk, for tests that must prove an
+// input reaches the edge it was built for. The token figures are those of the
+// Huffman form and stay zero for a stored chunk, whose tokens are not written.
+struct ChunkStats {
+  uint32_t tokens, matches;
+  bool trees_ok, stored;
+  uint32_t used_ll, used_d;           // symbols with a count
+  uint32_t nll, nd, ncl;              // HLIT + 257, HDIST + 1, HCLEN + 4
+  uint32_t max_ll_len, max_d_len;     // longest code of a used symbol
+  uint32_t max_dist, max_dist_code;   // over the matches
+  uint32_t len258;                    // matches of kMaxMatch
+  uint32_t max_token_bits;            // code and extra bits of the widest token
+  uint32_t three_word_puts;           // tokens with (pos & 31) + bits > 64
+  uint32_t three_word_nonzero;        // ... whose bits in the third word are not all zero
+  BuildSteps builder[3];              // lit/len, distance, code lengths
+  uint32_t builder_steps_max;
+};
+
+// One chunk (1 <= n <= kChunkBytes) through the parse, the builder and the
+// token walk of compress_chunk, writing nothing.
+inline ChunkStats chunk_stats(const uint8_t* b, uint32_t n) {
+  ChunkStats st{};
+  Trees t{};
+  std::vector<uint32_t> tokens;
+  parse_chunk(b, n, tokens, t);
+  st.tokens = static_cast<uint32_t>(tokens.size());
+  for (uint32_t tok : tokens) {
+    if (!(tok & kTokMatch)) continue;
+    uint32_t len = ((tok >> 16) & 0xFFu) + 3, dist = (tok & 0x7FFFu) + 1;
+    st.matches++;
+    st.len258 += len == kMaxMatch;
+    if (dist > st.max_dist) st.max_dist = dist, st.max_dist_code = dist_code(dist - 1);
+  }
+  for (uint32_t s = 0; s < kNumLL; s++) st.used_ll += t.hist_ll[s] != 0;
+  for (uint32_t s = 0; s < kNumD; s++) st.used_d += t.hist_d[s] != 0;
+  HeaderShape shape{};
+  uint32_t block_bits = 0;
+  st.trees_ok = build_trees(HostCtx{}, t, &shape, &block_bits, st.builder);
+  for (const BuildSteps& bs : st.builder)
+    if (bs.steps > st.builder_steps_max) st.builder_steps_max = bs.steps;
+  st.stored = !st.trees_ok || huffman_bytes(block_bits) >= chunk_bound(n);
+  if (!st.trees_ok) return st;
+  st.nll = shape.nll, st.nd = shape.nd, st.ncl = shape.ncl;
+  for (uint32_t s = 0; s < kNumLL; s++)
+    if (t.hist_ll[s] && t.len_ll[s] > st.max_ll_len) st.max_ll_len = t.len_ll[s];
+  for (uint32_t s = 0; s < kNumD; s++)
+    if (t.hist_d[s] && t.len_d[s] > st.max_d_len) st.max_d_len = t.len_d[s];
+  if (st.stored) return st;
+  uint32_t pos = header_bit_count(t, shape);
+  for (uint32_t tok : tokens) {
+    uint64_t v;
+    uint32_t nb = token_bits(t, tok, &v);
+    if (nb > st.max_token_bits) st.max_token_bits = nb;
+    if ((pos & 31u) + nb > 64) {
+      st.three_word_puts++;
+      st.three_word_nonzero += (v >> (64 - (pos & 31u))) != 0;
+    }
+    pos += nb;
+  }
+  return st;
 }
 
 inline void gzip_trailer(uint8_t* out, uint32_t crc, uint64_t size) {

@@ -227,5 +227,11 @@ hipError_t modelx_deflate_gather(const void* src, uint64_t size, uint64_t first_
                                  uint32_t nchunks, const void* slots,
                                  const modelx::abi::DeflateChunkOut* out_dev,
                                  const uint64_t* dst_addr_dev, hipStream_t stream);
+// deflate::build_lengths of the nsym (2..286) counts at hist_dev, each below
+// 2^16, to at most maxbits (1..15) bits, by one workgroup: the nsym lengths in
+// len_dev and the builder's return value in *ok_dev.
+hipError_t modelx_deflate_code_lengths(const uint32_t* hist_dev, uint32_t nsym, uint32_t maxbits,
+                                       int complete, uint8_t* len_dev, uint32_t* ok_dev,
+                                       hipStream_t stream);
 
 }  // extern "C"

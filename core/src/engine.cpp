@@ -119,6 +119,27 @@ void check_cdc_bits(const char* who, uint64_t bits) {
                                 std::to_string(bits) + " (1..24)");
 }
 
+// Most chunks one launch of the DEFLATE kernel takes, and the default of
+// gzip_compress_device's batch_chunks.
+constexpr uint64_t kGzipBatchChunks = 4096;
+
+// What deflate::build_lengths demands of a histogram from outside: an alphabet
+// of 2 to 286 symbols (the filler code needs a second symbol; the kernel's
+// staging holds 286), counts that fit the arg-max key, a limit of 1..15 bits.
+void check_code_lengths_args(const char* who, const std::vector<uint32_t>& hist,
+                             uint32_t maxbits) {
+  if (hist.size() < 2 || hist.size() > deflate::kNumLL)
+    throw std::invalid_argument(std::string(who) + ": " + std::to_string(hist.size()) +
+                                " symbols (2..286)");
+  if (maxbits < 1 || maxbits > deflate::kLLBits)
+    throw std::invalid_argument(std::string(who) + ": maxbits " + std::to_string(maxbits) +
+                                " (1..15)");
+  for (uint32_t c : hist)
+    if (c > 0xFFFFu)
+      throw std::invalid_argument(std::string(who) + ": count " + std::to_string(c) +
+                                  " does not fit 16 bits");
+}
+
 // The checks every AEAD entry point makes before it touches a byte: a 32-byte
 // key, a segment size aead_core.hpp accepts, at least one byte, and a segment
 // count the kernel's 32-bit mismatch index can hold.
@@ -918,10 +939,15 @@ class GpuEngine {
   // header; the chunk kernel also leaves each chunk's raw CRC-32, joined here
   // for the trailer. Runs on hash_stream_ and returns the stored size after it
   // has synchronised. dst_cap must be at least gzip_compress_bound(size).
+  // batch_chunks (1..4096) is the most chunks one launch takes.
   uint64_t gzip_compress_device(uintptr_t src_ptr, uint64_t size, uintptr_t dst_ptr,
-                                uint64_t dst_cap) {
+                                uint64_t dst_cap, uint64_t batch_chunks) {
     namespace df = modelx::deflate;
     using modelx::abi::DeflateChunkOut;
+    if (batch_chunks < 1 || batch_chunks > kGzipBatchChunks)
+      throw std::runtime_error("gzip_compress_device: batch_chunks " +
+                               std::to_string(batch_chunks) + " is outside 1.." +
+                               std::to_string(kGzipBatchChunks));
     const uint64_t bound = df::gzip_bound(size);
     if (dst_cap < bound)
       throw std::runtime_error("gzip_compress_device: dst_cap " + std::to_string(dst_cap) +
@@ -942,7 +968,7 @@ class GpuEngine {
     }
     uint64_t out = head.size();
     uint32_t reg = df::crc32::kInit;
-    const uint64_t batch = std::min<uint64_t>(nchunks, 4096);
+    const uint64_t batch = std::min<uint64_t>(nchunks, batch_chunks);
     if (batch) {
       void* dtokens = gz_tokens_.reserve(
           std::min<uint64_t>(batch, modelx::abi::kDeflateMaxBlocks) * df::kChunkBytes * 4);
@@ -983,6 +1009,31 @@ class GpuEngine {
                              hipMemcpyHostToDevice, hash_stream_));
     HIP_CHECK(hipStreamSynchronize(hash_stream_));
     return out + sizeof trailer;
+  }
+
+  // deflate::build_lengths of `hist` by one workgroup with the DEFLATE kernel's
+  // group context (core/hip/deflate_lengths.hip): (return value, lengths). The same
+  // arguments and the same answer as _core.deflate_code_lengths_host; the
+  // tests compare the two. Not part of any data path.
+  std::pair<bool, std::vector<uint8_t>> deflate_code_lengths_device(
+      const std::vector<uint32_t>& hist, uint32_t maxbits, bool complete) {
+    check_code_lengths_args("deflate_code_lengths_device", hist, maxbits);
+    HIP_CHECK(hipSetDevice(device_));
+    py::gil_scoped_release release;
+    const uint32_t nsym = static_cast<uint32_t>(hist.size());
+    const size_t len_off = nsym * sizeof(uint32_t), ok_off = (len_off + nsym + 3) / 4 * 4;
+    DeviceBuffer buf(ok_off + sizeof(uint32_t));
+    char* d = buf.get<char>();
+    HIP_CHECK(hipMemcpyAsync(d, hist.data(), len_off, hipMemcpyHostToDevice, hash_stream_));
+    HIP_CHECK(modelx_deflate_code_lengths(reinterpret_cast<const uint32_t*>(d), nsym, maxbits,
+                                          complete, reinterpret_cast<uint8_t*>(d + len_off),
+                                          reinterpret_cast<uint32_t*>(d + ok_off), hash_stream_));
+    HIP_CHECK(hipStreamSynchronize(hash_stream_));
+    std::vector<uint8_t> len(nsym);
+    uint32_t ok = 0;
+    HIP_CHECK(hipMemcpy(len.data(), d + len_off, nsym, hipMemcpyDeviceToHost));
+    HIP_CHECK(hipMemcpy(&ok, d + ok_off, sizeof ok, hipMemcpyDeviceToHost));
+    return {ok != 0, len};
   }
 
   // ------------------------------------------------------ byte planes ----
@@ -1829,7 +1880,15 @@ PYBIND11_MODULE(_core, m) {
       .def("byte_planes", &GpuEngine::byte_planes, py::arg("items"), py::arg("merge"))
       .def("crc32c_ranges", &GpuEngine::crc32c_ranges, py::arg("ranges"))
       .def("gzip_compress_device", &GpuEngine::gzip_compress_device, py::arg("src_ptr"),
-           py::arg("size"), py::arg("dst_ptr"), py::arg("dst_cap"))
+           py::arg("size"), py::arg("dst_ptr"), py::arg("dst_cap"),
+           py::arg("batch_chunks") = kGzipBatchChunks)
+      .def(
+          "deflate_code_lengths_device",
+          [](GpuEngine& e, const std::vector<uint32_t>& hist, uint32_t maxbits, bool complete) {
+            auto r = e.deflate_code_lengths_device(hist, maxbits, complete);
+            return py::make_tuple(r.first, std::vector<int>(r.second.begin(), r.second.end()));
+          },
+          py::arg("hist"), py::arg("maxbits"), py::arg("complete"))
       .def("aead_seal", &GpuEngine::aead_seal, py::arg("key32"), py::arg("src_ptr"),
            py::arg("n"), py::arg("dst_ptr"),
            py::arg("seg") = (uint64_t)aead::kDefaultSegmentBytes)
@@ -1951,6 +2010,66 @@ PYBIND11_MODULE(_core, m) {
       },
       py::arg("data"));
   m.def("gzip_compress_bound", &modelx::deflate::gzip_bound, py::arg("size"));
+  // Which paths the host model takes on one chunk (deflate::chunk_stats): what
+  // the tests assert about the payloads they build.
+  m.def(
+      "gzip_chunk_stats_host",
+      [](py::bytes data) {
+        namespace df = modelx::deflate;
+        std::string_view s = data;
+        if (s.empty() || s.size() > df::kChunkBytes)
+          throw std::invalid_argument("gzip_chunk_stats_host: one chunk of 1.." +
+                                      std::to_string(df::kChunkBytes) + " bytes");
+        df::ChunkStats st = df::chunk_stats(reinterpret_cast<const uint8_t*>(s.data()),
+                                            static_cast<uint32_t>(s.size()));
+        py::dict d;
+        d["tokens"] = st.tokens;
+        d["matches"] = st.matches;
+        d["trees_ok"] = st.trees_ok;
+        d["stored"] = st.stored;
+        d["used_ll"] = st.used_ll;
+        d["used_d"] = st.used_d;
+        d["nll"] = st.nll;
+        d["nd"] = st.nd;
+        d["ncl"] = st.ncl;
+        d["max_ll_len"] = st.max_ll_len;
+        d["max_d_len"] = st.max_d_len;
+        d["max_dist"] = st.max_dist;
+        d["max_dist_code"] = st.max_dist_code;
+        d["len258"] = st.len258;
+        d["max_token_bits"] = st.max_token_bits;
+        d["three_word_puts"] = st.three_word_puts;
+        d["three_word_nonzero"] = st.three_word_nonzero;
+        d["builder_steps_max"] = st.builder_steps_max;
+        py::dict steps, shrink;
+        const char* names[3] = {"ll", "d", "cl"};
+        for (int i = 0; i < 3; i++) {
+          steps[names[i]] = st.builder[i].steps;
+          shrink[names[i]] = st.builder[i].shrink;
+        }
+        d["builder_steps"] = steps;
+        d["builder_shrink_steps"] = shrink;
+        return d;
+      },
+      py::arg("data"));
+  // deflate::build_lengths on the host (a group of one thread): (return value,
+  // lengths, {"steps", "shrink"}). hist holds 2..286 counts below 2^16.
+  m.def(
+      "deflate_code_lengths_host",
+      [](const std::vector<uint32_t>& hist, uint32_t maxbits, bool complete) {
+        namespace df = modelx::deflate;
+        check_code_lengths_args("deflate_code_lengths_host", hist, maxbits);
+        std::vector<uint8_t> len(hist.size(), 0);
+        uint32_t cells[3];
+        df::BuildSteps bs{};
+        bool ok = df::build_lengths(df::HostCtx{}, hist.data(), static_cast<uint32_t>(hist.size()),
+                                    maxbits, complete, len.data(), cells, &bs);
+        py::dict steps;
+        steps["steps"] = bs.steps;
+        steps["shrink"] = bs.shrink;
+        return py::make_tuple(ok, std::vector<int>(len.begin(), len.end()), steps);
+      },
+      py::arg("hist"), py::arg("maxbits"), py::arg("complete"));
   m.attr("GZIP_CHUNK_BYTES") = modelx::deflate::kChunkBytes;
   // ChaCha20-Poly1305 sealed blobs on host bytes (aead_core.hpp): the model of
   // GpuEngine::aead_seal / aead_open and the CPU client's path. aead_open_host

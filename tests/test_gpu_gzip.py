@@ -1,14 +1,15 @@
 """gzip on the GPU: ``GpuEngine.gzip_compress_device`` (core/hip/deflate.hip)
 equals the host model of test_deflate byte for byte at every payload, length
-and source phase, and ``push_from_gpu(dir_format="tar+gz")`` end to end against
-modelx-s3d + modelxd."""
+and source phase, zlib inflates every one of its outputs, batches after the
+first are run at 1 to 7 chunks, the Huffman builder across one workgroup
+(core/hip/deflate_lengths.hip) equals the builder on the host, and
+``push_from_gpu(dir_format="tar+gz")`` end to end against modelx-s3d + modelxd."""
 import gc
 import gzip
 import hashlib
 import io
 import os
 import tarfile
-import zlib
 
 import pytest
 
@@ -18,7 +19,8 @@ from modelx_amd import _core
 from modelx_amd.wire import paths as pm
 from modelx_amd.wire import types as wt
 
-from test_deflate import C, LENGTHS, PAYLOADS, model, payload, words
+from test_deflate import (C, LENGTHS, OFFSETS, PAYLOADS, check_member, histograms, model,
+                          payload, words)
 from test_gpu_aead import stored_object, to_dev, to_host
 
 pytestmark = pytest.mark.gpu
@@ -34,24 +36,76 @@ def devs():
     return {name: to_dev(payload(name)) for name in PAYLOADS}
 
 
-def compress(engine, ptr, n):
+def compress(engine, ptr, n, **kw):
     """The member and the 16 guard bytes behind it."""
     bound = _core.gzip_compress_bound(n)
     out = torch.full((bound + 16,), 0xA5, dtype=torch.uint8, device="cuda:0")
-    stored = engine.gzip_compress_device(ptr, n, out.data_ptr(), bound)
+    stored = engine.gzip_compress_device(ptr, n, out.data_ptr(), bound, **kw)
     got = to_host(out)
     return got[:stored], got[stored:stored + 16]
 
 
-@pytest.mark.parametrize("offset", [0, 1, 5, 15])
+@pytest.mark.parametrize("offset", OFFSETS)
 @pytest.mark.parametrize("n", LENGTHS)
 @pytest.mark.parametrize("name", sorted(PAYLOADS))
 def test_device_equals_host_model(engine, devs, name, n, offset):
+    """Byte for byte the host model, and, so that a fault the two share cannot
+    hide, zlib inflates the device's bytes to the source at every case."""
     got, guard = compress(engine, devs[name].data_ptr() + offset, n)
+    check_member(got, payload(name)[offset:offset + n])
     assert got == model(name, offset, n)
     assert guard == b"\xa5" * 16
-    if name == "words" and n == 2 * C + 1041:
-        assert zlib.decompress(got, 31) == payload(name)[offset:offset + n]
+
+
+@pytest.mark.parametrize("part", range(4))
+def test_builder_on_device_equals_builder_on_host(engine, part):
+    """build_lengths across the 256 threads of one workgroup (the chunk
+    kernel's group context) against the group of one on the host, on the
+    histograms of test_deflate: the Kraft sum above one, complement keys and
+    keys with the top bits set, the fillers, up to 92 steps through the three
+    arg-max cells. One launch of one workgroup each."""
+    cases = histograms()[part::4]
+    assert len(cases) > 300
+    for hid, hist, maxbits, complete in cases:
+        ok, lens, _ = _core.deflate_code_lengths_host(hist, maxbits, complete)
+        assert engine.deflate_code_lengths_device(hist, maxbits, complete) == (ok, lens), hid
+
+
+def test_builder_on_device_refuses_what_it_cannot_hold(engine):
+    for hist, maxbits in (([1], 15), ([1] * 287, 15), ([1, 1], 0), ([1, 1], 16), ([65536, 1], 15)):
+        with pytest.raises(ValueError):
+            engine.deflate_code_lengths_device(hist, maxbits, True)
+
+
+@pytest.fixture(scope="module")
+def mixed():
+    """Seven chunks, stored (random) and Huffman (words) in turn, the last one
+    short, with room for the source phases."""
+    parts = [payload("random")[:C], words(7, C), words(8, C), payload("random")[C:2 * C],
+             words(9, C), payload("random")[100:100 + C], words(10, 5000)]
+    data = b"".join(parts) + bytes(16)
+    return data, to_dev(data)
+
+
+@pytest.mark.parametrize("offset", [0, 5])
+@pytest.mark.parametrize("batch_chunks", [1, 2, 3, 7])
+def test_later_batches(engine, mixed, batch_chunks, offset):
+    """Batches after the first: slots, sizes and addresses are indexed within
+    the batch, chunk offsets, BFINAL and the CRC join across it."""
+    data, dev = mixed
+    n = 6 * C + 5000
+    got, guard = compress(engine, dev.data_ptr() + offset, n, batch_chunks=batch_chunks)
+    assert got == _core.gzip_compress_host(data[offset:offset + n])
+    check_member(got, data[offset:offset + n])
+    assert guard == b"\xa5" * 16
+
+
+@pytest.mark.parametrize("batch_chunks", [0, 4097])
+def test_engine_refuses_a_bad_batch(engine, devs, batch_chunks):
+    out = torch.empty(4096, dtype=torch.uint8, device="cuda:0")
+    with pytest.raises(RuntimeError, match="batch_chunks"):
+        engine.gzip_compress_device(devs["words"].data_ptr(), 1000, out.data_ptr(), 4096,
+                                    batch_chunks=batch_chunks)
 
 
 def test_more_chunks_than_the_grid(engine):
