@@ -13,6 +13,7 @@
 #include "modelx/aead_core.hpp"
 #include "modelx/crc32c_core.hpp"
 #include "modelx/deflate_core.hpp"
+#include "modelx/inflate_core.hpp"
 #include "modelx/tar_core.hpp"
 #include "modelx/zstd_host.hpp"
 
@@ -127,6 +128,16 @@ struct DeflateChunkOut {
 constexpr uint32_t kDeflateMaxBlocks = 768;
 constexpr uint64_t kDeflateSlotStride = deflate::kChunkBytes + 16;
 
+// Marker scan of core/hip/inflate.hip: a workgroup owns kInflateScanTile bytes
+// on the 16 B grid of the member's first byte, as the candidate kernel's
+// tiles above. The CRC kernel takes the output in pieces of kInflateCrcPiece.
+constexpr uint32_t kInflateScanTile = 16u << 10;
+constexpr uint32_t kInflateCrcPiece = 32u << 10;
+
+inline uint32_t inflate_scan_tiles(uint64_t ptr, uint64_t size) {
+  return static_cast<uint32_t>(((ptr & 15u) + size + kInflateScanTile - 1) / kInflateScanTile);
+}
+
 }  // namespace abi
 }  // namespace modelx
 
@@ -233,5 +244,31 @@ hipError_t modelx_deflate_gather(const void* src, uint64_t size, uint64_t first_
 hipError_t modelx_deflate_code_lengths(const uint32_t* hist_dev, uint32_t nsym, uint32_t maxbits,
                                        int complete, uint8_t* len_dev, uint32_t* ok_dev,
                                        hipStream_t stream);
+// Candidates (modelx/inflate_core.hpp) of the gzip member of `size` bytes
+// (below 4 GiB) at src whose deflate stream is [first, limit). With cand_dev
+// null: counts_dev[k] is the number of markers that end in tile k. Otherwise
+// cand_dev[0] = first and tile k's positions, ascending, follow from
+// cand_dev[tile_base_dev[k]]; nothing is written at or past ncand. ntiles
+// must be inflate_scan_tiles(src, size). Reads no byte outside the 16 B
+// aligned words of the member.
+hipError_t modelx_inflate_scan(const void* src, uint64_t size, uint64_t first, uint64_t limit,
+                               uint32_t ntiles, uint32_t* counts_dev,
+                               const uint32_t* tile_base_dev, uint32_t* cand_dev, uint32_t ncand,
+                               hipStream_t stream);
+// inflate::decode_span from each of the ncand candidates, writing nothing but
+// recs_dev[i].
+hipError_t modelx_inflate_measure(const void* src, uint64_t size, uint64_t limit,
+                                  const uint32_t* cand_dev, uint32_t ncand,
+                                  modelx::inflate::SpanRec* recs_dev, hipStream_t stream);
+// Decodes span i of the plan into [dst + out_offset, ... + out_bytes) and
+// nowhere else, whatever the plan says; *err_dev (which the caller clears)
+// becomes nonzero if a span does not decode to exactly its out_bytes.
+hipError_t modelx_inflate_emit(const void* src, uint64_t size, uint64_t limit,
+                               const modelx::inflate::PlanSpan* plan_dev, uint32_t nspans,
+                               void* dst, uint32_t* err_dev, hipStream_t stream);
+// Raw CRC-32 (deflate::crc32) of every kInflateCrcPiece bytes of data, the
+// last piece short. Reads the 16 B aligned words that hold a byte of data.
+hipError_t modelx_crc32_pieces(const void* data, uint64_t total, uint32_t* out_dev,
+                               hipStream_t stream);
 
 }  // extern "C"

@@ -1036,6 +1036,155 @@ class GpuEngine {
     return {ok != 0, len};
   }
 
+  // ----------------------------------------------------------- gunzip ----
+
+  // What gunzip_plan_device found: the member's status (inflate::Status), and
+  // for an eligible member its size and the spans of its chain.
+  struct GunzipPlan {
+    uint32_t status = 0;
+    uint64_t out_bytes = 0;
+    std::vector<inflate::PlanSpan> spans;
+  };
+
+  // Plan the span-parallel inflate of the gzip member of `size` bytes at
+  // src_ptr (core/hip/inflate.hip; the rules and the host model are
+  // inflate_core.hpp's): the marker scan in two passes around a host prefix
+  // sum, one measuring wave per candidate, one D2H of the span table, and the
+  // chain walk on the host. Writes nothing but scratch and keeps no state: an
+  // ineligible member is a status, not an error. Runs on hash_stream_.
+  GunzipPlan gunzip_plan_device(uintptr_t src_ptr, uint64_t size) {
+    namespace inf = modelx::inflate;
+    if (src_ptr == 0 || src_ptr > UINTPTR_MAX - size)
+      throw std::runtime_error("gunzip_plan_device: null or wrapping range");
+    HIP_CHECK(hipSetDevice(device_));
+    py::gil_scoped_release release;
+    std::lock_guard<std::mutex> lk(gunzip_mu_);
+    GunzipPlan plan;
+    const void* src = reinterpret_cast<const void*>(src_ptr);
+    std::vector<uint8_t> head(std::min<uint64_t>(size, inf::kHeaderMax));
+    uint8_t tail[deflate::kGzipTrailerBytes] = {};
+    if (!head.empty()) HIP_CHECK(hipMemcpy(head.data(), src, head.size(), hipMemcpyDeviceToHost));
+    if (size >= sizeof tail)
+      HIP_CHECK(hipMemcpy(tail, static_cast<const char*>(src) + size - sizeof tail, sizeof tail,
+                          hipMemcpyDeviceToHost));
+    const inf::Member m = inf::parse_member(head.data(), tail, size);
+    if (m.status) {
+      plan.status = m.status;
+      return plan;
+    }
+    const uint32_t ntiles = modelx::abi::inflate_scan_tiles(src_ptr, size);
+    uint32_t* dcounts = gu_counts_.reserve<uint32_t>(ntiles * sizeof(uint32_t));
+    uint32_t* dbase = gu_base_.reserve<uint32_t>(ntiles * sizeof(uint32_t));
+    HIP_CHECK(modelx_inflate_scan(src, size, m.first, m.limit, ntiles, dcounts, nullptr, nullptr, 0,
+                                  hash_stream_));
+    HIP_CHECK(hipStreamSynchronize(hash_stream_));
+    std::vector<uint32_t> counts(ntiles), base(ntiles);
+    HIP_CHECK(hipMemcpy(counts.data(), dcounts, ntiles * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    uint64_t total = 1;  // entry 0 is the first deflate byte
+    for (uint32_t t = 0; t < ntiles; t++) {
+      base[t] = static_cast<uint32_t>(total);
+      total += counts[t];
+    }
+    const uint32_t ncand = static_cast<uint32_t>(total);  // below size / 4 + 1
+    uint32_t* dcand = gu_cand_.reserve<uint32_t>(ncand * sizeof(uint32_t));
+    inf::SpanRec* drecs = gu_recs_.reserve<inf::SpanRec>(ncand * sizeof(inf::SpanRec));
+    HIP_CHECK(hipMemcpyAsync(dbase, base.data(), ntiles * sizeof(uint32_t), hipMemcpyHostToDevice,
+                             hash_stream_));
+    HIP_CHECK(modelx_inflate_scan(src, size, m.first, m.limit, ntiles, nullptr, dbase, dcand, ncand,
+                                  hash_stream_));
+    HIP_CHECK(modelx_inflate_measure(src, size, m.limit, dcand, ncand, drecs, hash_stream_));
+    HIP_CHECK(hipStreamSynchronize(hash_stream_));
+    std::vector<uint32_t> cand(ncand);
+    std::vector<inf::SpanRec> recs(ncand);
+    HIP_CHECK(hipMemcpy(cand.data(), dcand, ncand * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    HIP_CHECK(hipMemcpy(recs.data(), drecs, ncand * sizeof(inf::SpanRec), hipMemcpyDeviceToHost));
+    const inf::ChainResult cr = inf::walk_chain(
+        m.first, m.limit, m.isize,
+        [&](uint64_t pos) -> const inf::SpanRec* {
+          auto it = std::lower_bound(cand.begin(), cand.end(), pos);
+          return it != cand.end() && *it == pos ? &recs[it - cand.begin()] : nullptr;
+        },
+        [&](uint64_t pos, const inf::SpanRec& rec, uint64_t out_offset) {
+          plan.spans.push_back({out_offset, rec.out_bytes, static_cast<uint32_t>(pos), 0});
+        });
+    plan.status = cr.status;
+    plan.out_bytes = cr.out_bytes;
+    if (cr.status) plan.spans.clear();
+    return plan;
+  }
+
+  // Inflate the member at src_ptr into dst_ptr by the spans of `plan` (what
+  // gunzip_plan_device returned for the same bytes), one emitting wave per
+  // span, then the CRC-32 of the output in pieces joined here and compared
+  // with the trailer. Returns the bytes written. Raises on a plan that is not
+  // a contiguous chain inside the member, a dst_cap below its size, an
+  // output that overlaps the source, a span that does not decode to its
+  // planned size, and a CRC-32 or ISIZE that differs; the kernel writes inside
+  // the planned spans only, whatever the plan holds.
+  uint64_t gunzip_emit_device(uintptr_t src_ptr, uint64_t size, std::string_view plan_bytes,
+                              uintptr_t dst_ptr, uint64_t dst_cap) {
+    namespace inf = modelx::inflate;
+    namespace crc = modelx::deflate::crc32;
+    if (src_ptr == 0 || dst_ptr == 0 || src_ptr > UINTPTR_MAX - size ||
+        dst_ptr > UINTPTR_MAX - dst_cap)
+      throw std::runtime_error("gunzip_emit_device: null or wrapping range");
+    if (size < deflate::kGzipHeaderBytes + deflate::kGzipTrailerBytes || size >= (1ull << 32))
+      throw std::runtime_error("gunzip_emit_device: no eligible member has " +
+                               std::to_string(size) + " bytes");
+    if (plan_bytes.empty() || plan_bytes.size() % sizeof(inf::PlanSpan))
+      throw std::runtime_error("gunzip_emit_device: the plan is not a list of spans");
+    std::vector<inf::PlanSpan> spans(plan_bytes.size() / sizeof(inf::PlanSpan));
+    std::memcpy(spans.data(), plan_bytes.data(), plan_bytes.size());
+    const uint64_t limit = size - deflate::kGzipTrailerBytes;
+    uint64_t total = 0;
+    for (const inf::PlanSpan& sp : spans) {
+      if (sp.in_start > limit || sp.out_offset != total || sp.out_bytes > UINT64_MAX - total)
+        throw std::runtime_error("gunzip_emit_device: the plan is not a chain of this member");
+      total += sp.out_bytes;
+    }
+    if (total > dst_cap)
+      throw std::runtime_error("gunzip_emit_device: dst_cap " + std::to_string(dst_cap) +
+                               " is below the member's " + std::to_string(total) + " bytes");
+    if (dst_cap && src_ptr < dst_ptr + dst_cap && dst_ptr < src_ptr + size)
+      throw std::runtime_error("gunzip_emit_device: source and destination overlap");
+    HIP_CHECK(hipSetDevice(device_));
+    py::gil_scoped_release release;
+    std::lock_guard<std::mutex> lk(gunzip_mu_);
+    const char* src = reinterpret_cast<const char*>(src_ptr);
+    uint8_t tail[deflate::kGzipTrailerBytes];
+    HIP_CHECK(hipMemcpy(tail, src + limit, sizeof tail, hipMemcpyDeviceToHost));
+    if (static_cast<uint32_t>(total) != deflate::load32(tail, 4))
+      throw std::runtime_error("gunzip_emit_device: the plan's size is not the trailer's ISIZE");
+    const uint32_t nspans = static_cast<uint32_t>(spans.size());
+    const uint64_t pieces = (total + modelx::abi::kInflateCrcPiece - 1) / modelx::abi::kInflateCrcPiece;
+    inf::PlanSpan* dplan = gu_plan_.reserve<inf::PlanSpan>(plan_bytes.size());
+    uint32_t* derr = gu_err_.reserve<uint32_t>(sizeof(uint32_t));
+    uint32_t* dcrc = gu_crc_.reserve<uint32_t>(std::max<uint64_t>(pieces, 1) * sizeof(uint32_t));
+    uint32_t err = 0;
+    HIP_CHECK(hipMemcpyAsync(dplan, spans.data(), plan_bytes.size(), hipMemcpyHostToDevice,
+                             hash_stream_));
+    HIP_CHECK(hipMemcpyAsync(derr, &err, sizeof err, hipMemcpyHostToDevice, hash_stream_));
+    HIP_CHECK(modelx_inflate_emit(src, size, limit, dplan, nspans,
+                                  reinterpret_cast<void*>(dst_ptr), derr, hash_stream_));
+    HIP_CHECK(modelx_crc32_pieces(reinterpret_cast<const void*>(dst_ptr), total, dcrc, hash_stream_));
+    HIP_CHECK(hipStreamSynchronize(hash_stream_));
+    HIP_CHECK(hipMemcpy(&err, derr, sizeof err, hipMemcpyDeviceToHost));
+    if (err)
+      throw std::runtime_error("gunzip emit kernel: a span did not decode to its planned size");
+    std::vector<uint32_t> raws(pieces);
+    if (pieces)
+      HIP_CHECK(hipMemcpy(raws.data(), dcrc, pieces * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    uint32_t reg = crc::kInit;
+    for (uint64_t i = 0; i < pieces; i++) {
+      uint64_t n = std::min<uint64_t>(modelx::abi::kInflateCrcPiece,
+                                      total - i * modelx::abi::kInflateCrcPiece);
+      reg = crc::mul_xn(reg, n, crc::pow_table()) ^ raws[i];
+    }
+    if ((reg ^ crc::kInit) != deflate::load32(tail, 0))
+      throw std::runtime_error("gunzip_emit_device: CRC-32 of the output differs from the trailer");
+    return total;
+  }
+
   // ------------------------------------------------------ byte planes ----
 
   // Byte-plane split (merge=false) or merge (merge=true) of device buffers
@@ -1805,6 +1954,8 @@ class GpuEngine {
   DeviceScratch cd_counts_, cd_lists_;
   std::mutex gzip_mu_;  // guards gzip_compress_device's scratch below
   DeviceScratch gz_tokens_, gz_slots_, gz_out_, gz_addr_;
+  std::mutex gunzip_mu_;  // guards the scratch of gunzip_plan_device and gunzip_emit_device
+  DeviceScratch gu_counts_, gu_base_, gu_cand_, gu_recs_, gu_plan_, gu_err_, gu_crc_;
 };
 
 bool hip_available() {
@@ -1889,6 +2040,27 @@ PYBIND11_MODULE(_core, m) {
             return py::make_tuple(r.first, std::vector<int>(r.second.begin(), r.second.end()));
           },
           py::arg("hist"), py::arg("maxbits"), py::arg("complete"))
+      .def(
+          "gunzip_plan_device",
+          [](GpuEngine& e, uintptr_t src_ptr, uint64_t size) {
+            auto plan = e.gunzip_plan_device(src_ptr, size);
+            py::dict d;
+            d["status"] = modelx::inflate::status_name(plan.status);
+            d["out_bytes"] = plan.out_bytes;
+            d["spans"] = plan.spans.size();
+            d["plan"] = py::bytes(reinterpret_cast<const char*>(plan.spans.data()),
+                                  plan.spans.size() * sizeof(modelx::inflate::PlanSpan));
+            return d;
+          },
+          py::arg("src_ptr"), py::arg("size"))
+      .def(
+          "gunzip_emit_device",
+          [](GpuEngine& e, uintptr_t src_ptr, uint64_t size, py::bytes plan, uintptr_t dst_ptr,
+             uint64_t dst_cap) {
+            return e.gunzip_emit_device(src_ptr, size, std::string_view(plan), dst_ptr, dst_cap);
+          },
+          py::arg("src_ptr"), py::arg("size"), py::arg("plan"), py::arg("dst_ptr"),
+          py::arg("dst_cap"))
       .def("aead_seal", &GpuEngine::aead_seal, py::arg("key32"), py::arg("src_ptr"),
            py::arg("n"), py::arg("dst_ptr"),
            py::arg("seg") = (uint64_t)aead::kDefaultSegmentBytes)
@@ -2071,6 +2243,44 @@ PYBIND11_MODULE(_core, m) {
       },
       py::arg("hist"), py::arg("maxbits"), py::arg("complete"));
   m.attr("GZIP_CHUNK_BYTES") = modelx::deflate::kChunkBytes;
+  // Span-parallel inflate of one gzip member on the host (inflate_core.hpp):
+  // (status, bytes), the model that gunzip_plan_device and gunzip_emit_device
+  // equal in status, span count and bytes. An ineligible member gives its
+  // status and no bytes. gzip_inflate_plan_host gives what the plan call
+  // reports: status, out_bytes and the number of spans on the chain.
+  m.def(
+      "gzip_inflate_spans_host",
+      [](py::bytes data) {
+        std::string_view s = data;
+        modelx::inflate::InflateResult r;
+        {
+          py::gil_scoped_release release;
+          r = modelx::inflate::gzip_inflate_spans(reinterpret_cast<const uint8_t*>(s.data()),
+                                                  s.size());
+        }
+        return py::make_tuple(modelx::inflate::status_name(r.status),
+                              py::bytes(reinterpret_cast<const char*>(r.bytes.data()),
+                                        r.bytes.size()));
+      },
+      py::arg("data"));
+  m.def(
+      "gzip_inflate_plan_host",
+      [](py::bytes data) {
+        std::string_view s = data;
+        modelx::inflate::InflateResult r;
+        {
+          py::gil_scoped_release release;
+          r = modelx::inflate::gzip_inflate_spans(reinterpret_cast<const uint8_t*>(s.data()),
+                                                  s.size());
+        }
+        py::dict d;
+        d["status"] = modelx::inflate::status_name(r.status);
+        d["out_bytes"] = r.bytes.size();
+        d["spans"] = r.spans;
+        return d;
+      },
+      py::arg("data"));
+  m.attr("GUNZIP_SPAN_MAX_CODED") = modelx::inflate::kSpanMaxCoded;
   // ChaCha20-Poly1305 sealed blobs on host bytes (aead_core.hpp): the model of
   // GpuEngine::aead_seal / aead_open and the CPU client's path. aead_open_host
   // returns the n plaintext bytes, or raises ValueError naming the first

@@ -27,6 +27,7 @@ to a CPU path.
 from __future__ import annotations
 
 import base64
+import gzip
 import os
 import sys
 import time
@@ -182,8 +183,12 @@ class GpuClient:
     def __init__(self, registry: str, authorization: str = "", device: int = 0,
                  num_slots: int = DEFAULT_NUM_SLOTS, slot_bytes: int = DEFAULT_SLOT_BYTES,
                  num_conns: int = DEFAULT_NUM_CONNS, dedup: bool = False, cdc=False,
-                 key: Optional[bytes] = None):
+                 key: Optional[bytes] = None, gpu_gunzip: bool = False):
         core = _core()
+        # tar+gz directory blobs land through the engine like every other blob
+        # and are inflated in HBM (core/hip/inflate.hip) instead of streamed
+        # through zlib on one core; see ``_gunzip_on_gpu``.
+        self.gpu_gunzip = gpu_gunzip
         # client-side encryption: the 32-byte key that ``push_from_gpu(...,
         # encrypt=True)`` seals blobs under and that pulls open sealed blobs
         # with (core/hip/aead.hip). It never leaves this process: each blob
@@ -913,9 +918,11 @@ class GpuClient:
         pull.go:184-203 pipes download∥extract): presigned GET (or registry
         stream) → zlib inflate → bounded pinned staging → HBM, with the
         STORED bytes digest-verified on the fly — host memory stays
-        O(staging), never O(blob). gzip is inherently sequential, so the
-        inflate runs on CPU; the GPU-native directory format
-        (MEDIA_TYPE_MODEL_DIRECTORY_TAR) skips this path entirely."""
+        O(staging), never O(blob). A gzip stream read front to back is
+        sequential, so this inflate runs on CPU; ``gpu_gunzip=True`` lands the
+        stored bytes in HBM and inflates them there (``_gunzip_on_gpu``), and
+        the GPU-native directory format (MEDIA_TYPE_MODEL_DIRECTORY_TAR) has
+        nothing to inflate."""
         import torch
 
         t0 = time.monotonic()
@@ -963,15 +970,20 @@ class GpuClient:
                         plan_entry=None) -> Dict[str, "torch.Tensor"]:
         """Land a directory blob and scatter its files into per-file HBM
         tensors with the CDNA4 tar kernels (core/hip/tar.hip). Plain-tar
-        blobs (MEDIA_TYPE_MODEL_DIRECTORY_TAR) stay on-GPU end to end;
-        tar+gz compat blobs are inflated on CPU first (gzip is sequential —
-        the GPU-native path is the plain-tar format). ``verify`` and
+        blobs (MEDIA_TYPE_MODEL_DIRECTORY_TAR) stay on-GPU end to end.
+        tar+gz blobs are by default streamed through zlib on the CPU
+        (``pull-targz-stream``); with ``gpu_gunzip=True`` they land like any
+        other blob and are inflated in HBM (``pull-gunzip``). ``verify`` and
         ``plan_entry`` are those of ``pull_blob_to_device`` and apply to
-        plain-tar blobs; the tar+gz stream always digests the stored bytes
-        as it goes and locates the blob itself."""
+        every blob that lands through it; the tar+gz stream always digests
+        the stored bytes as it goes and locates the blob itself."""
         if desc.media_type == types.MEDIA_TYPE_MODEL_DIRECTORY_TAR:
             archive = self.pull_blob_to_device(repository, desc, verify=verify,
                                                plan_entry=plan_entry)
+            tar_len = archive.numel()
+        elif desc.media_type == types.MEDIA_TYPE_MODEL_DIRECTORY_TARGZ and self.gpu_gunzip:
+            archive = self._gunzip_on_gpu(self.pull_blob_to_device(
+                repository, desc, verify=verify, plan_entry=plan_entry))
             tar_len = archive.numel()
         elif desc.media_type == types.MEDIA_TYPE_MODEL_DIRECTORY_TARGZ:
             archive, tar_len = self._stream_targz_to_device(repository, desc)
@@ -987,6 +999,40 @@ class GpuClient:
                 segs.append((int(e["offset"]), t.data_ptr(), int(e["size"])))
         if segs:
             self.engine.tar_scatter(archive.data_ptr(), segs)
+        return out
+
+    def _gunzip_on_gpu(self, stored: "torch.Tensor") -> "torch.Tensor":
+        """The bytes of the gzip member that landed in ``stored``, inflated in
+        HBM (core/hip/inflate.hip). The members this project writes, and any
+        stream whose pieces between sync markers do not depend on each other
+        (``pigz -i``, ``Z_FULL_FLUSH``), decode one wave per piece: the plan
+        call finds the pieces and their sizes, the output is allocated, the
+        emit call writes it and checks the CRC-32. That is the ``pull-gunzip``
+        phase of ``last_stats`` (``bytes`` the archive, ``stored_bytes``,
+        ``spans``). Any other member (a stock gzip stream, several members) is
+        inflated from the landed bytes by zlib on the host, recorded as
+        ``pull-gunzip-cpu`` with the plan's ``status``; nothing is downloaded
+        twice. While the member is inflated HBM holds it and its output; the
+        caller's reference to ``stored`` is the last one."""
+        import torch
+
+        t0 = time.monotonic()
+        size = stored.numel()
+        plan = self.engine.gunzip_plan_device(stored.data_ptr(), size)
+        if plan["status"] == "ok":
+            out = self._device(plan["out_bytes"])
+            self.engine.gunzip_emit_device(stored.data_ptr(), size, plan["plan"], out.data_ptr(),
+                                           out.numel())
+            self._stat("pull-gunzip", out.numel(), t0, stored_bytes=size, spans=plan["spans"])
+            return out
+        try:
+            raw = gzip.decompress(self.engine.read_device(stored.data_ptr(), size))
+        except (OSError, EOFError, zlib.error) as e:
+            raise er.ModelxError(er.ErrCode.UNKNOWN, f"tar+gz blob does not inflate: {e}")
+        out = self._device(len(raw))
+        if raw:
+            out.copy_(torch.frombuffer(bytearray(raw), dtype=torch.uint8))
+        self._stat("pull-gunzip-cpu", len(raw), t0, stored_bytes=size, status=plan["status"])
         return out
 
     def pack_dir_on_gpu(self, name: str, files: Dict[str, "torch.Tensor"]) -> "torch.Tensor":

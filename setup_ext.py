@@ -26,12 +26,13 @@ SOURCES = [
     "core/hip/aead.hip",
     "core/hip/deflate.hip",
     "core/hip/deflate_lengths.hip",
+    "core/hip/inflate.hip",
     "core/src/zstd_cpu.cpp",
     "core/src/http.cpp",
     "core/src/json.cpp",
 ]
 
-# crc32c.hip, cdc.hip, aead.hip and the deflate files are integer work throughout: keep the
+# crc32c.hip, cdc.hip, aead.hip and the deflate and inflate files are integer work throughout: keep the
 # compiler from forming packed fp32 instructions in them.
 _NO_PACKED_FP32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 EXTRA_FLAGS = {
@@ -40,6 +41,7 @@ EXTRA_FLAGS = {
     "core/hip/aead.hip": _NO_PACKED_FP32,
     "core/hip/deflate.hip": _NO_PACKED_FP32,
     "core/hip/deflate_lengths.hip": _NO_PACKED_FP32,
+    "core/hip/inflate.hip": _NO_PACKED_FP32,
 }
 
 
