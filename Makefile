@@ -25,7 +25,7 @@ $(BIN)/modelxd-asan: $(CORE_SRC) core/src/modelxd_main.cpp core/include/modelx/*
 
 $(BIN)/modelx-s3d-asan: $(CORE_SRC) core/src/s3d.cpp core/include/modelx/*.hpp
 	@mkdir -p $(BIN)
-	$(CXX) $(CXXFLAGS) -g -fsanitize=address $(INCLUDES) $(CORE_SRC) core/src/s3d.cpp -o $@ $(LIBS)
+	$(CXX) $(CXXFLAGS) -g -fsanitize=address,undefined $(INCLUDES) $(CORE_SRC) core/src/s3d.cpp -o $@ $(LIBS)
 
 $(BIN)/modelxd-tsan: $(CORE_SRC) core/src/modelxd_main.cpp core/include/modelx/*.hpp
 	@mkdir -p $(BIN)

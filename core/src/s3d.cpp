@@ -8,11 +8,14 @@
 // ListObjectsV2, and the multipart-upload lifecycle. SigV4 signatures are
 // verified for real — both auth paths prove the signer in sigv4.cpp against
 // an independent verifier.
+#include <dirent.h>
 #include <fcntl.h>
 #include <signal.h>
+#include <sys/ioctl.h>
 #include <sys/mman.h>
 #include <sys/sendfile.h>
 #include <sys/stat.h>
+#include <sys/statvfs.h>
 #include <unistd.h>
 
 #include <algorithm>
@@ -20,6 +23,7 @@
 #include <condition_variable>
 #include <cstring>
 #include <deque>
+#include <map>
 #include <mutex>
 #include <thread>
 #include <ctime>
@@ -108,18 +112,262 @@ std::string format_crc32c_header(uint32_t crc) {
   return v;
 }
 
+// ---- counters (GET /.metrics) ------------------------------------------------
+// Where a PUT lane's time goes: blocked on the client (socket side) or in the
+// store (file side: the copy plus tmpfs page setup), and what the trash
+// collector spends freeing pages. Sums over the process's life.
+struct Counters {
+  std::atomic<uint64_t> put_count{0}, put_bytes{0};
+  std::atomic<uint64_t> put_sock_ns{0}, put_file_ns{0};
+  std::atomic<uint64_t> trash_unlink_ns{0}, trash_unlinked{0};
+  // recycled files: PUTs served from the pool / not, files pooled, files
+  // refused because a GET had them open, times the pool was emptied for space
+  std::atomic<uint64_t> recycle_hits{0}, recycle_misses{0}, recycle_pooled{0};
+  std::atomic<uint64_t> recycle_busy{0}, recycle_drains{0};
+};
+Counters g_ctr;
+
+uint64_t now_ns() {
+  struct timespec ts;
+  clock_gettime(CLOCK_MONOTONIC, &ts);
+  return static_cast<uint64_t>(ts.tv_sec) * 1000000000ull + static_cast<uint64_t>(ts.tv_nsec);
+}
+
+// One PUT's share of the counters, added on whichever path the PUT leaves by.
+struct PutTimer {
+  uint64_t sock_ns = 0, file_ns = 0;
+  const int64_t* bytes;
+  explicit PutTimer(const int64_t* b) : bytes(b) {}
+  ~PutTimer() {
+    g_ctr.put_count++;
+    g_ctr.put_bytes += static_cast<uint64_t>(*bytes);
+    g_ctr.put_sock_ns += sock_ns;
+    g_ctr.put_file_ns += file_ns;
+  }
+};
+
+// ---- recycled files ----------------------------------------------------------
+// Deleted data files wait in <root>/.recycle/ for a PUT of their size class,
+// which overwrites their pages in place instead of allocating fresh ones: on
+// tmpfs that is the difference between a copy and a copy plus a page
+// allocation, memcg charge, xarray insert and LRU add per 4 KiB, with the
+// matching frees in the trash collector.
+//
+// The one hazard is a GET still reading a file that a PUT then overwrites.
+// Every data-file open of a GET goes through open_for_read, which counts the
+// reader on the file's inode under g_pool.mu; pool_offer checks that count
+// under the same lock and refuses a file that has readers (it is unlinked as
+// before, and its readers keep the old bytes). A file reaches pool_offer only
+// after defer_delete renamed it out of its object path, so an open that comes
+// after the check cannot reach that inode any more: opens are by object path.
+//
+// A reader does not end when sendfile returns: sendfile is zero-copy, and the
+// bytes the peer has not read yet sit in the socket buffers as references to
+// the file's pages, which a PUT into the recycled file would rewrite under
+// them. So the count stays until the peer has shown that it read the
+// response: its next request arrives on the same connection and was not
+// already on its way while the response was being sent (a pipelining client
+// proves nothing, its counts stay for good). A connection that ends, by
+// either side, proves nothing either: what it read last stays counted, and
+// such a file is unlinked when deleted, never pooled. t_conn holds one
+// connection's counts; the server runs one thread per connection.
+using FileId = std::pair<dev_t, ino_t>;
+
+struct Pool {
+  std::mutex mu;
+  std::multimap<int64_t, std::string> by_size;  // size -> path under .recycle/
+  int64_t bytes = 0;
+  std::map<FileId, int> readers;
+  uint64_t seq = 0;
+  // set once in main(), before the first thread starts
+  int64_t cap = 0;                // --recycle-cap-bytes; 0 = no pool
+  // --recycle-min-bytes. Below about a MiB (256 pages) a file's page setup
+  // costs less than the pool's rename and the index entry are worth.
+  int64_t min_bytes = 1 << 20;
+  // A multipart manifest is read by path without a reader count and is
+  // always below 8 KiB; nothing that small is ever pooled.
+  static constexpr int64_t kMinFloor = 8192;
+};
+Pool g_pool;
+
+std::string recycle_dir() { return g_cfg.root + "/.recycle"; }
+
+// A pooled file serves a PUT of `want` bytes when its size is in
+// [want, want + want/4]: the PUT truncates it to `want` at the end, and
+// freeing more than a quarter of it there would cost what recycling saves.
+// The file has left the index when this returns, so no second PUT gets it.
+std::string pool_take(int64_t want) {
+  if (want < g_pool.min_bytes) return "";
+  std::lock_guard<std::mutex> lk(g_pool.mu);
+  auto it = g_pool.by_size.lower_bound(want);
+  if (it == g_pool.by_size.end() || it->first > want + want / 4) {
+    g_ctr.recycle_misses++;
+    return "";
+  }
+  std::string file = it->second;
+  g_pool.bytes -= it->first;
+  g_pool.by_size.erase(it);
+  g_ctr.recycle_hits++;
+  return file;
+}
+
+// Moves a deleted file into the pool; false leaves it to the caller to unlink.
+bool pool_offer(const std::string& file, const struct stat& st) {
+  if (!S_ISREG(st.st_mode) || st.st_nlink != 1 || st.st_size < g_pool.min_bytes) return false;
+  std::lock_guard<std::mutex> lk(g_pool.mu);
+  if (g_pool.bytes + st.st_size > g_pool.cap) return false;
+  if (g_pool.readers.count(FileId(st.st_dev, st.st_ino))) {
+    g_ctr.recycle_busy++;
+    return false;
+  }
+  std::string dst = recycle_dir() + "/" + std::to_string(g_pool.seq++);
+  if (::rename(file.c_str(), dst.c_str()) != 0) return false;
+  g_pool.by_size.emplace(st.st_size, dst);
+  g_pool.bytes += st.st_size;
+  g_ctr.recycle_pooled++;
+  return true;
+}
+
+// Frees every pooled file (a PUT met ENOSPC).
+void pool_drain() {
+  std::multimap<int64_t, std::string> files;
+  {
+    std::lock_guard<std::mutex> lk(g_pool.mu);
+    files.swap(g_pool.by_size);
+    g_pool.bytes = 0;
+  }
+  for (auto& f : files) ::unlink(f.second.c_str());
+  g_ctr.recycle_drains++;
+}
+
+// True once per PUT when a write failed for lack of space and the pool has
+// been emptied to make some: the caller repeats the write.
+bool made_space(bool* retried) {
+  if (errno != ENOSPC || *retried) return false;
+  *retried = true;
+  pool_drain();
+  return true;
+}
+
+// The temporary file of a PUT of `want` bytes (<= 0: length unknown): a
+// recycled file renamed to `tmp` and opened as it is, or a fresh empty one.
+// A recycled file is at least `want` long; the caller writes from offset 0
+// and cuts it to length before renaming it into place.
+int open_put_tmp(const std::string& tmp, int64_t want, bool* recycled) {
+  *recycled = false;
+  std::string pooled = want > 0 ? pool_take(want) : "";
+  if (!pooled.empty()) {
+    if (::rename(pooled.c_str(), tmp.c_str()) == 0) {
+      int fd = ::open(tmp.c_str(), O_RDWR | O_CLOEXEC);
+      if (fd >= 0) {
+        *recycled = true;
+        return fd;
+      }
+      ::unlink(tmp.c_str());
+    } else {
+      ::unlink(pooled.c_str());
+    }
+  }
+  return ::open(tmp.c_str(), O_RDWR | O_CREAT | O_TRUNC | O_CLOEXEC, 0644);
+}
+
+// The reader counts of this thread's connection that may still be dropped.
+struct ConnReads {
+  std::vector<FileId> held;
+  bool pipelined = false;  // seen once, the connection's counts all stay
+};
+thread_local ConnReads t_conn;
+
+// Opens a data file for a GET and counts the reader on its inode, under
+// g_pool.mu (see above). The caller closes the descriptor; the count stays
+// with the connection until reads_consumed().
+int open_for_read(const std::string& path) {
+  std::lock_guard<std::mutex> lk(g_pool.mu);
+  int fd = ::open(path.c_str(), O_RDONLY | O_CLOEXEC);
+  if (fd < 0) return -1;
+  struct stat st;
+  if (::fstat(fd, &st) != 0) {
+    ::close(fd);
+    return -1;
+  }
+  FileId id(st.st_dev, st.st_ino);
+  g_pool.readers[id]++;
+  t_conn.held.push_back(id);
+  return fd;
+}
+
+// After a GET's last byte went to the socket: request bytes that are already
+// here were sent without waiting for this response, so this client's later
+// requests say nothing about what it has read.
+void reads_sent(http::Request& req) {
+  if (t_conn.held.empty() || t_conn.pipelined) return;
+  int sock = req.raw_fd_if_plain();  // -1: TLS, or bytes wait in the buffer
+  int pending = 0;
+  if (sock < 0 || ::ioctl(sock, FIONREAD, &pending) != 0 || pending > 0) t_conn.pipelined = true;
+}
+
+// A new request arrived on this connection: the peer has read the responses
+// before it, and the files they came from may be pooled again.
+void reads_consumed() {
+  if (t_conn.held.empty()) return;
+  if (!t_conn.pipelined) {
+    std::lock_guard<std::mutex> lk(g_pool.mu);
+    for (auto& id : t_conn.held) {
+      auto it = g_pool.readers.find(id);
+      if (it != g_pool.readers.end() && --it->second == 0) g_pool.readers.erase(it);
+    }
+  }
+  t_conn.held.clear();
+}
+
+std::string render_metrics() {
+  auto secs = [](const std::atomic<uint64_t>& ns) { return std::to_string(ns.load() * 1e-9); };
+  std::string m;
+  {
+    std::lock_guard<std::mutex> lk(g_pool.mu);
+    m += "s3d_recycle_pool_bytes " + std::to_string(g_pool.bytes) + "\n";
+    m += "s3d_recycle_pool_files " + std::to_string(g_pool.by_size.size()) + "\n";
+  }
+  m += "s3d_recycle_cap_bytes " + std::to_string(g_pool.cap) + "\n";
+  m += "s3d_recycle_min_bytes " + std::to_string(g_pool.min_bytes) + "\n";
+  m += "s3d_recycle_hits_total " + std::to_string(g_ctr.recycle_hits.load()) + "\n";
+  m += "s3d_recycle_misses_total " + std::to_string(g_ctr.recycle_misses.load()) + "\n";
+  m += "s3d_recycle_pooled_total " + std::to_string(g_ctr.recycle_pooled.load()) + "\n";
+  m += "s3d_recycle_busy_total " + std::to_string(g_ctr.recycle_busy.load()) + "\n";
+  m += "s3d_recycle_drains_total " + std::to_string(g_ctr.recycle_drains.load()) + "\n";
+  m += "s3d_put_total " + std::to_string(g_ctr.put_count.load()) + "\n";
+  m += "s3d_put_bytes_total " + std::to_string(g_ctr.put_bytes.load()) + "\n";
+  m += "s3d_put_socket_seconds_total " + secs(g_ctr.put_sock_ns) + "\n";
+  m += "s3d_put_file_seconds_total " + secs(g_ctr.put_file_ns) + "\n";
+  m += "s3d_trash_unlink_seconds_total " + secs(g_ctr.trash_unlink_ns) + "\n";
+  m += "s3d_trash_unlinked_total " + std::to_string(g_ctr.trash_unlinked.load()) + "\n";
+  return m;
+}
+
 // Stores the request body at `path` through a temporary file. With
 // `expect_crc32c` the body goes through user space (no splice), is
 // checksummed as it is written, and is renamed into place only if its
 // CRC-32C is *expect_crc32c; a mismatch removes the temporary file, sets
-// *bad_digest and returns false.
+// *bad_digest and returns false. The temporary file is a recycled one when
+// the pool has one of the body's size class (open_put_tmp); a write that
+// fails with ENOSPC empties the pool and is repeated once.
 bool write_stream_to(const std::string& path, http::Request& req, std::string* etag,
                      const uint32_t* expect_crc32c = nullptr, bool* bad_digest = nullptr) {
   if (!mkdirs_for(path)) return false;
   std::string tmp = path + ".tmp" + std::to_string(getpid());
-  int fd = ::open(tmp.c_str(), O_RDWR | O_CREAT | O_TRUNC | O_CLOEXEC, 0644);
+  bool recycled = false;
+  int fd = open_put_tmp(tmp, req.content_length, &recycled);
   if (fd < 0) return false;
   int64_t total = 0;
+  PutTimer timer(&total);
+  bool retried = false;  // made_space: one retry per PUT
+  // Closes the temporary file, cut to the body's length where it came from
+  // the pool (a recycled file may be longer and then holds a stale tail).
+  auto close_at_length = [&]() {
+    bool ok = !recycled || ::ftruncate(fd, total) == 0;
+    ::close(fd);
+    return ok;
+  };
   // NOTE: an mmap+recv variant (ftruncate, MAP_SHARED, recv into the
   // mapping) was A/B-tested on the GPU box and LOST to plain write() on the
   // tmpfs store: per-page fault handling in the recv copy path costs more
@@ -140,7 +388,7 @@ bool write_stream_to(const std::string& path, http::Request& req, std::string* e
       ssize_t off = 0;
       while (off < r) {
         ssize_t w = ::write(fd, small + off, static_cast<size_t>(r - off));
-        if (w < 0 && errno == EINTR) continue;
+        if (w < 0 && (errno == EINTR || made_space(&retried))) continue;
         if (w < 0) {
           // counting unwritten bytes would let a short object pass the
           // completeness check below and be renamed into place
@@ -159,19 +407,24 @@ bool write_stream_to(const std::string& path, http::Request& req, std::string* e
         fcntl(pfd[0], F_SETPIPE_SZ, 1 << 20);
         int64_t rem = req.body_remaining;
         while (rem > 0) {
+          uint64_t t0 = now_ns();
           ssize_t r = ::splice(sock, nullptr, pfd[1], nullptr,
                                static_cast<size_t>(std::min<int64_t>(rem, 1 << 20)),
                                SPLICE_F_MOVE | SPLICE_F_MORE);
+          uint64_t t1 = now_ns();
+          timer.sock_ns += t1 - t0;
           if (r < 0 && errno == EINTR) continue;
           if (r <= 0) break;
           ssize_t moved = 0;
           while (moved < r) {
             ssize_t w = ::splice(pfd[0], nullptr, fd, nullptr,
                                  static_cast<size_t>(r - moved), SPLICE_F_MOVE);
-            if (w < 0 && errno == EINTR) continue;
+            // the bytes are still in the pipe after a failed splice
+            if (w < 0 && (errno == EINTR || made_space(&retried))) continue;
             if (w <= 0) { moved = -1; break; }
             moved += w;
           }
+          timer.file_ns += now_ns() - t1;
           if (moved < 0) break;
           rem -= r;
           total += r;
@@ -181,8 +434,7 @@ bool write_stream_to(const std::string& path, http::Request& req, std::string* e
         ::close(pfd[1]);
       }
     }
-    ::close(fd);
-    if (total != req.content_length) {
+    if (!close_at_length() || total != req.content_length) {
       ::unlink(tmp.c_str());
       return false;
     }
@@ -196,7 +448,10 @@ bool write_stream_to(const std::string& path, http::Request& req, std::string* e
   std::vector<char> buf(4 << 20);
   uint32_t crc = crc32c::kInit;
   while (true) {
+    uint64_t t0 = now_ns();
     ssize_t r = req.read_body(buf.data(), buf.size());
+    uint64_t t1 = now_ns();
+    timer.sock_ns += t1 - t0;
     if (r < 0) {
       ::close(fd);
       ::unlink(tmp.c_str());
@@ -208,17 +463,17 @@ bool write_stream_to(const std::string& path, http::Request& req, std::string* e
     while (off < r) {
       ssize_t w = ::write(fd, buf.data() + off, static_cast<size_t>(r - off));
       if (w < 0) {
-        if (errno == EINTR) continue;
+        if (errno == EINTR || made_space(&retried)) continue;
         ::close(fd);
         ::unlink(tmp.c_str());
         return false;
       }
       off += w;
     }
+    timer.file_ns += now_ns() - t1;
     total += r;
   }
-  ::close(fd);
-  if (total != req.content_length) {
+  if (!close_at_length() || total != req.content_length) {
     ::unlink(tmp.c_str());
     return false;
   }
@@ -358,6 +613,31 @@ void defer_delete(const std::string& path) {
   }
 }
 
+// Disposes of one trashed path: a directory (an object's parts) file by
+// file, a file into the recycle pool where it qualifies, else unlinked.
+void collect(const std::string& victim) {
+  struct stat st;
+  if (::lstat(victim.c_str(), &st) != 0) return;
+  if (S_ISDIR(st.st_mode)) {
+    std::vector<std::string> names;
+    if (DIR* d = ::opendir(victim.c_str())) {
+      while (struct dirent* e = ::readdir(d)) {
+        std::string n = e->d_name;
+        if (n != "." && n != "..") names.push_back(n);
+      }
+      ::closedir(d);
+    }
+    for (auto& n : names) collect(victim + "/" + n);
+    ::rmdir(victim.c_str());
+    return;
+  }
+  if (pool_offer(victim, st)) return;
+  uint64_t t0 = now_ns();
+  ::unlink(victim.c_str());
+  g_ctr.trash_unlink_ns += now_ns() - t0;
+  g_ctr.trash_unlinked++;
+}
+
 void trash_collector() {
   while (true) {
     std::string victim;
@@ -367,13 +647,7 @@ void trash_collector() {
       victim = g_trash_queue.front();
       g_trash_queue.pop_front();
     }
-    struct stat st;
-    if (::lstat(victim.c_str(), &st) == 0) {
-      if (S_ISDIR(st.st_mode))
-        store::LocalFSProvider(g_cfg.root).Remove(victim.substr(g_cfg.root.size() + 1), true);
-      else
-        ::unlink(victim.c_str());
-    }
+    collect(victim);
   }
 }
 
@@ -528,6 +802,7 @@ void complete_multipart(http::Request& req, http::ResponseWriter& w, const std::
       manifest += std::to_string((long long)st.st_size) + " " + p.second + "\n";
     }
     std::string tmp = dest + ".tmp" + std::to_string(getpid());
+    // a fresh file: a manifest is below the smallest file the pool keeps
     int out = ok ? ::open(tmp.c_str(), O_WRONLY | O_CREAT | O_TRUNC | O_CLOEXEC, 0644) : -1;
     if (out >= 0) {
       ok = ::write(out, manifest.data(), manifest.size()) ==
@@ -551,8 +826,14 @@ void complete_multipart(http::Request& req, http::ResponseWriter& w, const std::
 }
 
 void handle(http::Request& req, http::ResponseWriter& w) {
+  reads_consumed();
   if (req.path == "/healthz") {
     w.write_all(200, "ok");
+    return;
+  }
+  // counters only, open like /healthz; a dot name can be no bucket's
+  if (req.path == "/.metrics" && req.method == "GET") {
+    w.write_all(200, render_metrics(), "text/plain; version=0.0.4");
     return;
   }
   if (!authorized(req)) {
@@ -569,7 +850,8 @@ void handle(http::Request& req, http::ResponseWriter& w) {
   size_t slash = p.find('/', 1);
   std::string bucket = slash == std::string::npos ? p.substr(1) : p.substr(1, slash - 1);
   std::string key = slash == std::string::npos ? "" : p.substr(slash + 1);
-  if (bucket.empty()) {
+  // .mpu, .trash and .recycle hold the server's own files, never objects
+  if (bucket.empty() || bucket[0] == '.') {
     w.write_all(404, "no bucket");
     return;
   }
@@ -701,7 +983,7 @@ void handle(http::Request& req, http::ResponseWriter& w) {
     if (req.method == "GET") {
       bool delivered = false;
       if (!is_parts) {
-        int fd = ::open(path.c_str(), O_RDONLY | O_CLOEXEC);
+        int fd = open_for_read(path);
         if (fd >= 0) {
           delivered = w.sendfile(fd, start, length);
           ::close(fd);
@@ -718,7 +1000,7 @@ void handle(http::Request& req, http::ResponseWriter& w) {
           }
           int64_t in_off = cursor - pos;
           int64_t take = std::min(psize - in_off, remaining);
-          int fd = ::open(part.second.c_str(), O_RDONLY | O_CLOEXEC);
+          int fd = open_for_read(part.second);
           if (fd < 0) break;
           bool ok = w.sendfile(fd, in_off, take);
           ::close(fd);
@@ -733,6 +1015,7 @@ void handle(http::Request& req, http::ResponseWriter& w) {
       // desynced — close the connection so the client fails loudly and
       // retries, instead of reading the next response as body bytes
       if (!delivered) w.abort_connection();
+      reads_sent(req);
     }
     return;
   }
@@ -753,6 +1036,7 @@ void handle(http::Request& req, http::ResponseWriter& w) {
 int main(int argc, char** argv) {
   std::string listen = ":9000";
   http::TlsConfig tls;
+  int64_t recycle_cap = -1;  // -1: derive from the filesystem below
   for (int i = 1; i < argc; i++) {
     std::string a = argv[i];
     auto next = [&]() -> std::string { return i + 1 < argc ? argv[++i] : ""; };
@@ -764,15 +1048,31 @@ int main(int argc, char** argv) {
     else if (a == "--no-auth") g_cfg.verify_auth = false;
     else if (a == "--tls-cert") tls.cert_file = next();
     else if (a == "--tls-key") tls.key_file = next();
+    else if (a == "--recycle-cap-bytes") recycle_cap = atoll(next().c_str());
+    else if (a == "--recycle-min-bytes")
+      g_pool.min_bytes = std::max<int64_t>(Pool::kMinFloor, atoll(next().c_str()));
     else if (a == "--help" || a == "-h") {
       printf("modelx-s3d: S3-compatible test/bench object server\n"
              "  --listen :9000  --root data/s3  --access-key K --secret-key S\n"
-             "  --region us-east-1  --no-auth  --tls-cert F --tls-key F\n");
+             "  --region us-east-1  --no-auth  --tls-cert F --tls-key F\n"
+             "  --recycle-cap-bytes N (default: 1/4 of the root's free space; 0 = off)\n"
+             "  --recycle-min-bytes N (default 1 MiB, at least 8 KiB)\n");
       return 0;
     }
   }
   signal(SIGPIPE, SIG_IGN);
   mkdirs_for(g_cfg.root + "/.");
+  // nothing under these two outlives the process that put it there
+  store::LocalFSProvider(g_cfg.root).Remove(".trash", true);
+  store::LocalFSProvider(g_cfg.root).Remove(".recycle", true);
+  mkdirs_for(recycle_dir() + "/.");
+  if (recycle_cap < 0) {
+    struct statvfs vfs;
+    recycle_cap = ::statvfs(g_cfg.root.c_str(), &vfs) == 0
+                      ? static_cast<int64_t>(vfs.f_bavail) * static_cast<int64_t>(vfs.f_frsize) / 4
+                      : 0;
+  }
+  g_pool.cap = recycle_cap;
   std::thread(trash_collector).detach();
   http::Server server(listen, handle, tls);
   int port = server.start();
@@ -787,5 +1087,9 @@ int main(int argc, char** argv) {
   int sig = 0;
   sigwait(&set, &sig);
   server.stop();
-  return 0;
+  // The collector and the connection threads are detached and still use the
+  // globals above; returning would run their destructors under them (a
+  // condition variable with a waiter never finishes being destroyed).
+  fflush(nullptr);
+  _exit(0);
 }

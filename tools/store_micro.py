@@ -2,7 +2,9 @@
 """A/B the object-store backing, PUT-then-immediately-GET (the bench
 pattern). Mount-free variants (gpurun boxes refuse mounts): existing
 /dev/shm (tmpfs) vs the scratch disk. Pass a mount-opts string as a third
-variant only where mounting is permitted."""
+variant only where mounting is permitted. --warm: one tmpfs store whose
+objects are deleted through s3d between reps, so rep1 PUTs into recycled
+files; s3d's /.metrics counters are printed after each rep."""
 import os
 import subprocess
 import sys
@@ -20,7 +22,7 @@ from util_servers import S3D, free_port, wait_http
 SIZE = 8 << 30
 
 
-def bench_store(tag, root_base=None, mount_opts=None):
+def bench_store(tag, root_base=None, mount_opts=None, warm=False):
     if mount_opts:
         root = f"/mnt/modelx-{tag}"
         os.makedirs(root, exist_ok=True)
@@ -61,8 +63,24 @@ def bench_store(tag, root_base=None, mount_opts=None):
             t_pull = time.monotonic() - t0
             print(f"{tag} rep{rep}: push {SIZE / t_push / (1 << 30):.1f} GiB/s, "
                   f"pull {SIZE / t_pull / (1 << 30):.1f} GiB/s")
-            for i in range(8):
-                os.unlink(f"{root}/modelx/o{i}")
+            if warm:
+                # DELETE through s3d: the files go to its recycle pool, so the
+                # next rep's PUTs overwrite their pages (rep0 cold, rep1 warm)
+                import requests
+
+                for i in range(8):
+                    requests.delete(f"{base}/o{i}")
+                deadline = time.monotonic() + 10
+                while time.monotonic() < deadline:
+                    m = requests.get(f"http://127.0.0.1:{port}/.metrics").text
+                    # the pull connections still count the object they read last
+                    if "s3d_recycle_pool_files 7\n" in m or "s3d_recycle_pool_files 8\n" in m:
+                        break
+                    time.sleep(0.01)
+                print(f"{tag} rep{rep} s3d counters:\n{m}")
+            else:
+                for i in range(8):
+                    os.unlink(f"{root}/modelx/o{i}")
     finally:
         proc.terminate()
         proc.wait()
@@ -75,6 +93,10 @@ def bench_store(tag, root_base=None, mount_opts=None):
 
 
 if __name__ == "__main__":
+    if "--warm" in sys.argv:
+        # cold (rep0) and recycled (rep1) PUTs side by side, tmpfs only
+        bench_store("shm-warm", root_base="/dev/shm", warm=True)
+        sys.exit(0)
     bench_store("shm", root_base="/dev/shm")
     bench_store("disk", root_base="/tmp")
     bench_store("hugetmpfs", mount_opts="size=48g,huge=always")
