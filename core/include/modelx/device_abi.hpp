@@ -133,6 +133,12 @@ constexpr uint64_t kDeflateSlotStride = deflate::kChunkBytes + 16;
 // tiles above. The CRC kernel takes the output in pieces of kInflateCrcPiece.
 constexpr uint32_t kInflateScanTile = 16u << 10;
 constexpr uint32_t kInflateCrcPiece = 32u << 10;
+// Block search of core/hip/inflate.hip: the deflate stream is cut every
+// kInflateSearchStride bytes after its first byte, one workgroup per stride,
+// which it stages kInflateSearchTile bytes at a time.
+constexpr uint32_t kInflateSearchStride = 64u << 10;
+constexpr uint32_t kInflateSearchTile = 4u << 10;
+static_assert(kInflateSearchStride % kInflateSearchTile == 0, "a stride is whole tiles");
 
 inline uint32_t inflate_scan_tiles(uint64_t ptr, uint64_t size) {
   return static_cast<uint32_t>(((ptr & 15u) + size + kInflateScanTile - 1) / kInflateScanTile);
@@ -266,6 +272,32 @@ hipError_t modelx_inflate_measure(const void* src, uint64_t size, uint64_t limit
 hipError_t modelx_inflate_emit(const void* src, uint64_t size, uint64_t limit,
                                const modelx::inflate::PlanSpan* plan_dev, uint32_t nspans,
                                void* dst, uint32_t* err_dev, hipStream_t stream);
+// Block search (modelx/inflate_core.hpp, "search") of the same member:
+// slots_dev takes two words per stride, nstrides = inflate::search_strides at
+// kInflateSearchStride; cand_dev (1 + 2 * nstrides words) takes the sorted
+// candidates, the stream's first bit as entry 0, and *ncand_dev their number.
+// Reads no byte outside the 16 B aligned words of the member.
+hipError_t modelx_inflate_search(const void* src, uint64_t size, uint64_t first, uint64_t limit,
+                                 uint32_t nstrides, uint64_t* slots_dev, uint64_t* cand_dev,
+                                 uint32_t* ncand_dev, hipStream_t stream);
+// inflate::decode_span with ListCut from each candidate into its symbolic ring,
+// rings_dev + i * kWindow (uint16 entries), leaving recs_dev[i].
+hipError_t modelx_inflate_measure_search(const void* src, uint64_t size, uint64_t limit,
+                                         const uint64_t* cand_dev, uint32_t ncand,
+                                         uint16_t* rings_dev, modelx::inflate::SpanRec* recs_dev,
+                                         hipStream_t stream);
+// Resolves the windows of the nspans chain spans in order: windows_dev + j *
+// kWindow is what span j reads before its first byte (zeros for span 0).
+hipError_t modelx_inflate_windows(const uint16_t* rings_dev,
+                                  const modelx::inflate::ChainLink* chain_dev, uint32_t nspans,
+                                  uint8_t* windows_dev, hipStream_t stream);
+// modelx_inflate_emit for a search plan: span i starts at the candidate in
+// in_start and pad_, ends where span i + 1 starts, and reads matches that
+// reach before it from windows_dev + i * kWindow.
+hipError_t modelx_inflate_emit_search(const void* src, uint64_t size, uint64_t limit,
+                                      const modelx::inflate::PlanSpan* plan_dev, uint32_t nspans,
+                                      const uint8_t* windows_dev, void* dst, uint32_t* err_dev,
+                                      hipStream_t stream);
 // Raw CRC-32 (deflate::crc32) of every kInflateCrcPiece bytes of data, the
 // last piece short. Reads the 16 B aligned words that hold a byte of data.
 hipError_t modelx_crc32_pieces(const void* data, uint64_t total, uint32_t* out_dev,

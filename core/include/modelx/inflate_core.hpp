@@ -40,6 +40,9 @@
 // for the trailer), `too-large` (4 GiB and above). Candidates off the chain
 // are false markers and are ignored.
 //
+// A stream without markers is `too-long` or `dependent` by these rules; the
+// section "search" at the end of this file decodes it from found block starts.
+//
 // Group. decode_span is called by every thread of a group with the same
 // arguments, like deflate::build_lengths. Thread 0 owns the bit reader and
 // decodes; what the others need it leaves in Work::ctl. The group fills the
@@ -50,8 +53,10 @@
 // deflate_core.hpp; the sink takes them a batch at a time.
 #pragma once
 
+#include <algorithm>
 #include <cstddef>
 #include <cstdint>
+#include <utility>
 #include <vector>
 
 #include "modelx/deflate_core.hpp"
@@ -89,12 +94,61 @@ struct SpanRec {
   uint32_t status;  // Status | kFinal
 };
 
-// One span of the chain, as the emitting kernel takes it.
+// Block search (gunzip of streams without markers; see "search" below). A
+// candidate is key << 1 | kind: kind 0 a block header whose first bit is at
+// bit position `key`, kind 1 a stored block whose LEN field is at byte key / 8.
+// A span that ends at a candidate leaves the candidate's byte in `end` and its
+// low four bits (bit in the byte, kind) in the status from kEndShift up.
+constexpr uint32_t kWindow = 32768;      // deflate's history
+constexpr uint32_t kUnknown = 0x8000u;   // | k: byte k of the window a span was not given
+constexpr uint32_t kCutHere = 0x80u;     // thread 0 -> group inside decode_span only
+constexpr uint32_t kEndShift = 16;
+constexpr uint64_t kNoCand = ~0ull;
+
+MX_HD inline uint64_t make_cand(uint64_t bit, bool stored) { return bit << 1 | (stored ? 1u : 0u); }
+MX_HD inline uint64_t end_cand(const SpanRec& rec) {
+  return static_cast<uint64_t>(rec.end) << 4 | ((rec.status >> kEndShift) & 15u);
+}
+
+struct MarkerCut {
+  static constexpr bool kSearch = false;
+  MX_HD bool hit(uint64_t) { return false; }
+};
+// Ends the span at the first candidate of the sorted list, from `cur` on, that
+// a block of the span's own chain starts at; the ones it passes are not on it.
+struct ListCut {
+  static constexpr bool kSearch = true;
+  const uint64_t* cand;
+  uint32_t n, cur;
+  MX_HD bool hit(uint64_t c) {
+    while (cur < n && cand[cur] < c) cur++;
+    return cur < n && cand[cur] == c;
+  }
+};
+// Ends the span where the plan says the next one starts.
+struct EndCut {
+  static constexpr bool kSearch = true;
+  uint64_t end;
+  MX_HD bool hit(uint64_t c) const { return c == end; }
+};
+
+// One span of the chain, as the emitting kernel takes it. In a search plan
+// pad_ holds the low four bits of the span's candidate (in_start its byte).
 struct PlanSpan {
   uint64_t out_offset;
   uint64_t out_bytes;
   uint32_t in_start;
   uint32_t pad_;
+};
+
+MX_HD inline uint64_t plan_cand(const PlanSpan& sp) {
+  return static_cast<uint64_t>(sp.in_start) << 4 | (sp.pad_ & 15u);
+}
+
+// One span of a search's chain, as the window kernel takes it: which ring, and
+// out_bytes % kWindow, where the window behind the span starts in it.
+struct ChainLink {
+  uint32_t ring, rot;
 };
 
 // Tokens that are neither literal nor match.
@@ -310,22 +364,44 @@ MX_HD inline uint32_t read_lengths(const Ctx& cx, BitReader& r, Tables& t, LenSt
 // 512 bytes on, or everything). Sink: stored(cx, at, len, out) copies a stored
 // block's bytes, tokens(cx, tok, n, &out) takes a batch, adds what it
 // produces to `out` and returns a status; `out` counts the span's bytes.
-template <class Ctx, class Sink>
-MX_HD inline SpanRec decode_span(Ctx& cx, Work& w, Sink& sink, uint64_t start, uint64_t limit) {
+//
+// The span starts at the candidate `start` (make_cand: a block header at a bit
+// position, or the LEN field of a stored block whose header is taken as
+// BFINAL=0). Cut says where it ends short of BFINAL. MarkerCut: after an empty
+// stored block, as above. A searching Cut (kSearch) is asked by thread 0, with
+// the candidate that every later block without BFINAL would start as, in
+// stream order; the first hit ends the span before that block, and empty
+// stored blocks are blocks like any other.
+template <class Ctx, class Sink, class Cut>
+MX_HD inline SpanRec decode_span(Ctx& cx, Work& w, Sink& sink, uint64_t start, uint64_t limit,
+                                 Cut& cut) {
+  const uint64_t start_bit = start >> 1;
+  const bool at_len = (start & 1u) != 0;
   BitReader r;  // thread 0's
-  r.init(start, limit);
-  uint64_t out = 0, coded = 0, at = start, end = 0;
+  r.init(start_bit >> 3, limit);
+  uint64_t out = 0, coded = 0, at = start_bit >> 3, end = 0;
   uint32_t status = kOk;
+  bool first = true, cut_here = false;
   for (;;) {
     uint64_t safe = cx.refill(at);
     LenState ls{kMaxLL, kMaxD, 0};
     uint64_t block_start = 0;
     if (cx.tid == 0) {
       r.fill(cx);
+      if (first) r.drop(static_cast<uint32_t>(start_bit & 7u));
       block_start = r.bit_pos();
-      uint32_t bfinal = r.take(1), btype = r.take(2), st = kOk, n = 0;
+      uint32_t bfinal = 0, btype = 0, st = kOk, n = 0;
       uint64_t p = 0;
-      if (btype == 0) {
+      if (!(first && at_len)) {
+        bfinal = r.take(1), btype = r.take(2);
+        if (Cut::kSearch && !first && !bfinal) {
+          const uint64_t c = btype == 0 ? make_cand((r.bit_pos() + 7) / 8 * 8, true)
+                                        : make_cand(block_start, false);
+          if (cut.hit(c)) st = kCutHere, p = c;
+        }
+      }
+      if (st) {  // the span ends before this block
+      } else if (btype == 0) {
         r.drop(r.cnt & 7u);
         r.fill(cx);
         n = r.take(16);
@@ -356,7 +432,13 @@ MX_HD inline SpanRec decode_span(Ctx& cx, Work& w, Sink& sink, uint64_t start, u
     cx.sync();
     status = w.ctl[0];
     const uint32_t btype = w.ctl[1], bfinal = w.ctl[2];
+    if (status == kCutHere) {
+      end = w.ctl[4] | static_cast<uint64_t>(w.ctl[5]) << 32;
+      status = kOk, cut_here = true;
+      break;
+    }
     if (status) break;
+    first = false;
     at = w.ctl[6] | static_cast<uint64_t>(w.ctl[7]) << 32;
     if (btype == 0) {
       const uint32_t n = w.ctl[3];
@@ -367,7 +449,7 @@ MX_HD inline SpanRec decode_span(Ctx& cx, Work& w, Sink& sink, uint64_t start, u
         if (status) break;
         out += n;
       }
-      if (!n || bfinal) {
+      if ((!Cut::kSearch && !n) || bfinal) {
         end = p + n;
         if (bfinal) status = kFinal;
         break;
@@ -446,7 +528,16 @@ MX_HD inline SpanRec decode_span(Ctx& cx, Work& w, Sink& sink, uint64_t start, u
     }
   }
   if (status & kStatusMask) return SpanRec{0, 0, status};
+  if (cut_here)  // `end` is the candidate the next span starts at
+    return SpanRec{out, static_cast<uint32_t>(end >> 4),
+                   static_cast<uint32_t>(end & 15u) << kEndShift};
   return SpanRec{out, static_cast<uint32_t>(end), status};
+}
+
+template <class Ctx, class Sink>
+MX_HD inline SpanRec decode_span(Ctx& cx, Work& w, Sink& sink, uint64_t start, uint64_t limit) {
+  MarkerCut cut;
+  return decode_span(cx, w, sink, make_cand(start * 8, false), limit, cut);
 }
 
 // ---- chain ------------------------------------------------------------------
@@ -460,14 +551,14 @@ struct ChainResult {
 // Follows the chain from `first`: span_at(pos) gives the record of the span
 // that starts at the candidate pos, or nullptr if there is none; on_span(pos,
 // rec, out_offset) sees every ok span of the chain in order.
-template <class SpanAt, class OnSpan>
+template <class SpanAt, class OnSpan, class EndOf>
 inline ChainResult walk_chain(uint64_t first, uint64_t limit, uint32_t isize, SpanAt span_at,
-                              OnSpan on_span) {
+                              OnSpan on_span, EndOf end_of) {
   ChainResult cr{kOk, 0, 0};
   for (uint64_t pos = first;;) {
     const SpanRec* rec = span_at(pos);
     uint32_t st = rec ? rec->status & kStatusMask : kCorrupt;
-    if (!st && rec->end <= pos) st = kCorrupt;  // a span consumes at least one block
+    if (!st && end_of(*rec) <= pos) st = kCorrupt;  // a span consumes at least one block
     if (st) return ChainResult{st, 0, 0};
     on_span(pos, *rec, cr.out_bytes);
     cr.spans++;
@@ -476,10 +567,19 @@ inline ChainResult walk_chain(uint64_t first, uint64_t limit, uint32_t isize, Sp
       if (rec->end != limit) return ChainResult{kTrailing, 0, 0};
       break;
     }
-    pos = rec->end;
+    pos = end_of(*rec);
   }
   if (static_cast<uint32_t>(cr.out_bytes) != isize) return ChainResult{kCorrupt, 0, 0};
   return cr;
+}
+
+// The chain over byte positions (markers); with search_end as EndOf the same
+// walk runs over the candidates of a search.
+template <class SpanAt, class OnSpan>
+inline ChainResult walk_chain(uint64_t first, uint64_t limit, uint32_t isize, SpanAt span_at,
+                              OnSpan on_span) {
+  return walk_chain(first, limit, isize, span_at, on_span,
+                    [](const SpanRec& rec) -> uint64_t { return rec.end; });
 }
 
 // Header length, stream limit and trailer of a member of `size` bytes whose
@@ -553,6 +653,271 @@ inline InflateResult gzip_inflate_spans(const uint8_t* data, uint64_t size) {
       },
       [](uint64_t, const SpanRec&, uint64_t) {});
   res.status = cr.status, res.spans = cr.spans;
+  if (!res.status &&
+      (deflate::crc32::update(deflate::crc32::kInit, res.bytes.data(), res.bytes.size()) ^
+       deflate::crc32::kInit) != m.crc)
+    res.status = kCorrupt;
+  if (res.status) res.spans = 0, res.bytes.clear();
+  return res;
+}
+
+// ---- search -----------------------------------------------------------------
+//
+// A stream without markers (stock gzip, Z_SYNC_FLUSH) is cut at a fixed stride
+// after its first byte: boundary k is first + k * stride, k >= 1, and stride k
+// runs from it to the next boundary or the stream end. In every stride the
+// first position of each kind that can start a block becomes a candidate:
+//   dynamic  a bit position with BFINAL=0, BTYPE=2, HLIT and HDIST <= 29, an
+//            exactly complete code length code (dynamic_plausible: 17 header
+//            bits and the Kraft sum of up to 19 three-bit lengths, one
+//            position per thread), and then lengths that read without a bad
+//            repeat or an overrun, an end-of-block code and two codes that
+//            count_lengths accepts (dynamic_confirm, by the group, with the
+//            functions decode_span itself uses)
+//   stored   a byte p with LEN == ~NLEN at p, the top three bits of byte p-1
+//            zero, and one hop: byte p+4+LEN is inside the stream, holds a
+//            block type other than 3, and if that block is stored too its
+//            LEN and NLEN agree
+// Fixed blocks are not searched for; the span that reaches one decodes it.
+// The sorted list starts with the stream's first bit and holds at most two
+// candidates per stride.
+//
+// A span of a search decodes into a ring of kWindow uint16 entries instead of
+// nowhere: entry k starts as kUnknown | k, "byte k of the window before my
+// first byte" (k = kWindow - distance), literals and stored bytes are plain
+// values, a match copies entries, so what a span takes from before its start
+// stays symbolic and nothing is `dependent`. Byte o of the span lies at
+// ring[o % kWindow]. In the span at the stream start a distance beyond its own
+// output is corrupt. ListCut ends a span at the first candidate its own chain
+// of blocks reaches; a candidate it passes is not on the chain (a false
+// candidate never is: a key that a block of the chain starts at with the
+// candidate's kind is a block start).
+//
+// Resolve, in chain order: R[0] is empty, and with T[j][k] = ring j's entry
+// (out_bytes j + k) % kWindow, the window behind span j,
+//   R[j+1][k] = T[j][k] plain ? T[j][k] : R[j][T[j][k] & 0x7FFF].
+// The emitting pass decodes span j again with EndCut and reads a match that
+// reaches d bytes before its first output byte from R[j][kWindow - d]. The
+// CRC-32 and ISIZE decide as before.
+
+// The 80 bits from bit position `bit` on: [0] the first 64, [1] the rest.
+template <class Ctx>
+MX_HD inline void load_bits80(const Ctx& cx, uint64_t bit, uint64_t limit, uint64_t* v) {
+  const uint64_t p = bit >> 3;
+  const uint32_t s = static_cast<uint32_t>(bit & 7u);
+  uint64_t lo = 0, hi = 0;
+  for (uint32_t i = 0; i < 8; i++)
+    if (p + i < limit) lo |= static_cast<uint64_t>(cx.byte(p + i)) << (8 * i);
+  for (uint32_t i = 0; i < 3; i++)
+    if (p + 8 + i < limit) hi |= static_cast<uint64_t>(cx.byte(p + 8 + i)) << (8 * i);
+  v[0] = s ? lo >> s | hi << (64 - s) : lo;
+  v[1] = hi >> s;
+}
+
+// The cheap part of the dynamic test. One thread, registers only.
+template <class Ctx>
+MX_HD inline bool dynamic_plausible(const Ctx& cx, uint64_t bit, uint64_t limit) {
+  uint64_t v[2];
+  load_bits80(cx, bit, limit, v);
+  if ((v[0] & 7u) != 4u) return false;  // BFINAL=0, BTYPE=2
+  if (((v[0] >> 3) & 31u) > 29u || ((v[0] >> 8) & 31u) > 29u) return false;
+  const uint32_t ncl = 4 + static_cast<uint32_t>((v[0] >> 13) & 15u);
+  if (bit + 17 + 3 * ncl > limit * 8) return false;
+  uint64_t lens = v[0] >> 17 | v[1] << 47;  // 57 bits of lengths at most
+  uint32_t kraft = 0;
+  for (uint32_t i = 0; i < ncl; i++, lens >>= 3)
+    if (lens & 7u) kraft += 128u >> (lens & 7u);
+  return kraft == 128u;
+}
+
+// The whole dynamic test at a plausible position, by the group. cx.byte must
+// serve the 576 bytes from the position's byte on (the longest header is 4498
+// bits, and the reader loads 8 bytes ahead).
+template <class Ctx>
+MX_HD inline bool dynamic_confirm(Ctx& cx, Work& w, uint64_t bit, uint64_t limit) {
+  BitReader r;  // thread 0's
+  LenState ls{0, 0, 0};
+  r.init(bit >> 3, limit);
+  if (cx.tid == 0) {
+    r.fill(cx);
+    r.drop(static_cast<uint32_t>(bit & 7u) + 3);
+    ls.nll = 257 + r.take(5), ls.nd = 1 + r.take(5);
+    const uint32_t ncl = 4 + r.take(4);
+    for (uint32_t i = 0; i < deflate::kNumCL; i++) w.t.len[i] = 0;
+    for (uint32_t i = 0; i < ncl; i++) {
+      r.fill(cx);
+      w.t.len[deflate::kCLOrder[i]] = static_cast<uint8_t>(r.take(3));
+    }
+    w.ctl[0] = !r.past() && ls.nll <= deflate::kNumLL && ls.nd <= deflate::kNumD &&
+               count_lengths(w.t.len, deflate::kNumCL, w.t.count_d, kCodeLengths);
+  }
+  cx.sync();
+  bool ok = w.ctl[0] != 0;
+  cx.sync();
+  if (!ok) return false;
+  fill_table(cx, w.t.len, deflate::kNumCL, w.t.count_d, w.t.sorted_d, w.t.d, kCLBits);
+  if (cx.tid == 0)
+    w.ctl[0] = read_lengths(cx, r, w.t, ls, ~0ull) == 1 && w.t.len[256] != 0 &&
+               count_lengths(w.t.len, ls.nll, w.t.count_ll, kCodeLL) &&
+               count_lengths(w.t.len + ls.nll, ls.nd, w.t.count_d, kCodeD);
+  cx.sync();
+  ok = w.ctl[0] != 0;
+  cx.sync();
+  return ok;
+}
+
+// LEN == ~NLEN at p and the byte before: `near` serves bytes p-1 .. p+3.
+template <class Near>
+MX_HD inline bool stored_plausible(const Near& near, uint64_t p, uint64_t limit) {
+  if (p == 0 || p + 4 > limit) return false;
+  const uint32_t len = near.byte(p) | static_cast<uint32_t>(near.byte(p + 1)) << 8;
+  const uint32_t nlen = near.byte(p + 2) | static_cast<uint32_t>(near.byte(p + 3)) << 8;
+  return len == (~nlen & 0xFFFFu) && !(near.byte(p - 1) & 0xE0u);
+}
+// The hop: `far` serves any byte below limit.
+template <class Far>
+MX_HD inline bool stored_confirm(const Far& far, uint64_t p, uint64_t limit) {
+  const uint64_t q = p + 4 + (far.byte(p) | static_cast<uint32_t>(far.byte(p + 1)) << 8);
+  if (q >= limit) return false;
+  const uint32_t btype = (far.byte(q) >> 1) & 3u;
+  if (btype == 3) return false;
+  if (btype != 0) return true;
+  if (q + 5 > limit) return false;
+  const uint32_t len = far.byte(q + 1) | static_cast<uint32_t>(far.byte(q + 2)) << 8;
+  const uint32_t nlen = far.byte(q + 3) | static_cast<uint32_t>(far.byte(q + 4)) << 8;
+  return len == (~nlen & 0xFFFFu);
+}
+
+MX_HD inline uint64_t search_strides(uint64_t first, uint64_t limit, uint64_t stride) {
+  return limit > first ? (limit - first - 1) / stride : 0;
+}
+
+// Ring entry k of the window behind a span of `out` bytes, resolved against
+// the window `prev` behind the span before it.
+MX_HD inline uint8_t resolve_entry(const uint16_t* ring, uint64_t out, uint32_t k,
+                                   const uint8_t* prev) {
+  const uint32_t e = ring[(out + k) & (kWindow - 1)];
+  return static_cast<uint8_t>(e & kUnknown ? prev[e & (kWindow - 1)] : e);
+}
+
+// The sorted candidates of the stream [first, limit) of data. Group of one.
+inline std::vector<uint64_t> search_candidates(const uint8_t* data, uint64_t first, uint64_t limit,
+                                               uint64_t stride) {
+  std::vector<uint64_t> cand{make_cand(first * 8, false)};
+  HostCtx cx{data};
+  Work w;
+  for (uint64_t k = 1, n = search_strides(first, limit, stride); k <= n; k++) {
+    const uint64_t from = first + k * stride, to = from + stride < limit ? from + stride : limit;
+    uint64_t dyn = kNoCand, sto = kNoCand;
+    for (uint64_t bit = from * 8; bit < to * 8 && dyn == kNoCand; bit++)
+      if (dynamic_plausible(cx, bit, limit) && dynamic_confirm(cx, w, bit, limit))
+        dyn = make_cand(bit, false);
+    for (uint64_t p = from; p < to && sto == kNoCand; p++)
+      if (stored_plausible(cx, p, limit) && stored_confirm(cx, p, limit)) sto = make_cand(p * 8, true);
+    if (dyn > sto) std::swap(dyn, sto);
+    if (dyn != kNoCand) cand.push_back(dyn);
+    if (sto != kNoCand) cand.push_back(sto);
+  }
+  return cand;
+}
+
+// What end_of of walk_chain takes from a record of a search.
+inline uint64_t search_end(const SpanRec& rec) {
+  return rec.status & kFinal ? make_cand(static_cast<uint64_t>(rec.end) * 8, false) : end_cand(rec);
+}
+
+// Measuring sink of a search: the symbolic ring.
+struct HostRingSink {
+  uint16_t* ring;
+  bool at_stream_start;
+  uint32_t stored(const HostCtx& cx, uint64_t at, uint32_t n, uint64_t out) {
+    for (uint32_t k = 0; k < n; k++) ring[(out + k) & (kWindow - 1)] = cx.data[at + k];
+    return kOk;
+  }
+  uint32_t tokens(const HostCtx&, const uint32_t* tok, uint32_t n, uint64_t* produced) {
+    uint64_t o = *produced;
+    for (uint32_t i = 0; i < n; i++) {
+      if (!(tok[i] & deflate::kTokMatch)) {
+        ring[o++ & (kWindow - 1)] = static_cast<uint8_t>(tok[i]);
+        continue;
+      }
+      uint32_t len = ((tok[i] >> 16) & 0xFFu) + 3, dist = (tok[i] & 0x7FFFu) + 1;
+      if (at_stream_start && dist > o) return kCorrupt;
+      for (uint32_t k = 0; k < len; k++, o++) ring[o & (kWindow - 1)] = ring[(o - dist) & (kWindow - 1)];
+    }
+    *produced = o;
+    return kOk;
+  }
+};
+
+// Emitting sink of a search: matches that reach before the span read `win`.
+struct HostWindowSink {
+  std::vector<uint8_t>& out;
+  size_t base;
+  const uint8_t* win;  // nullptr at the stream start
+  uint32_t stored(const HostCtx& cx, uint64_t at, uint32_t n, uint64_t) {
+    out.insert(out.end(), cx.data + at, cx.data + at + n);
+    return kOk;
+  }
+  uint32_t tokens(const HostCtx&, const uint32_t* tok, uint32_t n, uint64_t* produced) {
+    for (uint32_t i = 0; i < n; i++) {
+      if (!(tok[i] & deflate::kTokMatch)) {
+        out.push_back(static_cast<uint8_t>(tok[i]));
+        continue;
+      }
+      uint32_t len = ((tok[i] >> 16) & 0xFFu) + 3, dist = (tok[i] & 0x7FFFu) + 1;
+      if (!win && dist > out.size() - base) return kCorrupt;
+      for (uint32_t k = 0; k < len; k++) {
+        const size_t have = out.size() - base;
+        out.push_back(dist > have ? win[kWindow - (dist - have)] : out[out.size() - dist]);
+      }
+    }
+    *produced = out.size() - base;
+    return kOk;
+  }
+};
+
+// The host model of a search: candidates, one symbolic ring per span of the
+// chain, the chain walk, then resolve and emit span by span.
+inline InflateResult gzip_inflate_search(const uint8_t* data, uint64_t size, uint64_t stride) {
+  InflateResult res{kOk, 0, {}};
+  Member m = parse_member(data, size >= 8 ? data + size - 8 : data, size);
+  if (m.status) return res.status = m.status, res;
+  const std::vector<uint64_t> cand = search_candidates(data, m.first, m.limit, stride);
+  struct Link {
+    uint64_t start, out_bytes;
+    std::vector<uint16_t> ring;
+  };
+  std::vector<Link> chain;
+  Work w;
+  SpanRec rec;
+  HostCtx cx{data};
+  std::vector<uint16_t> ring(kWindow);
+  ChainResult cr = walk_chain(
+      cand[0], m.limit, m.isize,
+      [&](uint64_t pos) -> const SpanRec* {
+        auto it = std::lower_bound(cand.begin(), cand.end(), pos);
+        if (it == cand.end() || *it != pos) return nullptr;
+        for (uint32_t k = 0; k < kWindow; k++) ring[k] = static_cast<uint16_t>(kUnknown | k);
+        HostRingSink sink{ring.data(), pos == cand[0]};
+        ListCut cut{cand.data(), static_cast<uint32_t>(cand.size()),
+                    static_cast<uint32_t>(it - cand.begin()) + 1};
+        rec = decode_span(cx, w, sink, pos, m.limit, cut);
+        return &rec;
+      },
+      [&](uint64_t pos, const SpanRec& r, uint64_t) { chain.push_back({pos, r.out_bytes, ring}); },
+      search_end);
+  res.status = cr.status, res.spans = cr.spans;
+  std::vector<uint8_t> win(kWindow, 0), next(kWindow);
+  for (size_t j = 0; j < chain.size() && !res.status; j++) {
+    HostWindowSink sink{res.bytes, res.bytes.size(), j ? win.data() : nullptr};
+    EndCut cut{j + 1 < chain.size() ? chain[j + 1].start : kNoCand};
+    rec = decode_span(cx, w, sink, chain[j].start, m.limit, cut);
+    if ((rec.status & kStatusMask) || rec.out_bytes != chain[j].out_bytes) res.status = kCorrupt;
+    for (uint32_t k = 0; k < kWindow; k++)
+      next[k] = resolve_entry(chain[j].ring.data(), chain[j].out_bytes, k, win.data());
+    win.swap(next);
+  }
   if (!res.status &&
       (deflate::crc32::update(deflate::crc32::kInit, res.bytes.data(), res.bytes.size()) ^
        deflate::crc32::kInit) != m.crc)

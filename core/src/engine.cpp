@@ -1044,7 +1044,12 @@ class GpuEngine {
     uint32_t status = 0;
     uint64_t out_bytes = 0;
     std::vector<inflate::PlanSpan> spans;
+    uint64_t generation = 0;  // of a search plan: whose windows the spans need
   };
+
+  // A search plan's bytes are its spans behind one record of the same size
+  // that no chain can start with: {kSearchPlanMagic, generation, 0, 0}.
+  static constexpr uint64_t kSearchPlanMagic = 0x6e616c7068637273ull;  // "srchplan"
 
   // Plan the span-parallel inflate of the gzip member of `size` bytes at
   // src_ptr (core/hip/inflate.hip; the rules and the host model are
@@ -1052,7 +1057,17 @@ class GpuEngine {
   // sum, one measuring wave per candidate, one D2H of the span table, and the
   // chain walk on the host. Writes nothing but scratch and keeps no state: an
   // ineligible member is a status, not an error. Runs on hash_stream_.
-  GunzipPlan gunzip_plan_device(uintptr_t src_ptr, uint64_t size) {
+  //
+  // search=true plans a member without markers (inflate_core.hpp, "search"):
+  // block search and compaction, one D2H of the candidate count, one measuring
+  // wave per candidate into its symbolic ring, the chain walk on the host over
+  // candidates, and the window kernel over the chain. The resolved windows
+  // stay in this engine's scratch until the next plan call of either kind;
+  // the plan carries that call's generation number. Scratch: 64 KiB of ring
+  // per candidate and 32 KiB of window per chain span, at most two candidates
+  // and one span per kInflateSearchStride of the stream and one more of each:
+  // below 2.5 times the stored size plus 96 KiB.
+  GunzipPlan gunzip_plan_device(uintptr_t src_ptr, uint64_t size, bool search = false) {
     namespace inf = modelx::inflate;
     if (src_ptr == 0 || src_ptr > UINTPTR_MAX - size)
       throw std::runtime_error("gunzip_plan_device: null or wrapping range");
@@ -1068,10 +1083,13 @@ class GpuEngine {
       HIP_CHECK(hipMemcpy(tail, static_cast<const char*>(src) + size - sizeof tail, sizeof tail,
                           hipMemcpyDeviceToHost));
     const inf::Member m = inf::parse_member(head.data(), tail, size);
+    gu_generation_++;  // whatever this call finds, earlier search plans are stale
+    gu_window_spans_ = 0;
     if (m.status) {
       plan.status = m.status;
       return plan;
     }
+    if (search) return gunzip_plan_search(src, size, m);
     const uint32_t ntiles = modelx::abi::inflate_scan_tiles(src_ptr, size);
     uint32_t* dcounts = gu_counts_.reserve<uint32_t>(ntiles * sizeof(uint32_t));
     uint32_t* dbase = gu_base_.reserve<uint32_t>(ntiles * sizeof(uint32_t));
@@ -1113,6 +1131,65 @@ class GpuEngine {
     return plan;
   }
 
+  // The search half of gunzip_plan_device; gunzip_mu_ is held.
+  GunzipPlan gunzip_plan_search(const void* src, uint64_t size, const inflate::Member& m) {
+    namespace inf = modelx::inflate;
+    GunzipPlan plan;
+    const uint32_t nstrides = static_cast<uint32_t>(
+        inf::search_strides(m.first, m.limit, modelx::abi::kInflateSearchStride));
+    uint64_t* dslots = gu_slots_.reserve<uint64_t>((2ull * nstrides + 1) * sizeof(uint64_t));
+    uint64_t* dcand = gu_cand_.reserve<uint64_t>((2ull * nstrides + 1) * sizeof(uint64_t));
+    uint32_t* dncand = gu_err_.reserve<uint32_t>(sizeof(uint32_t));
+    HIP_CHECK(modelx_inflate_search(src, size, m.first, m.limit, nstrides, dslots, dcand, dncand,
+                                    hash_stream_));
+    HIP_CHECK(hipStreamSynchronize(hash_stream_));
+    uint32_t ncand = 0;
+    HIP_CHECK(hipMemcpy(&ncand, dncand, sizeof ncand, hipMemcpyDeviceToHost));
+    if (ncand < 1 || ncand > 2ull * nstrides + 1)
+      throw std::runtime_error("gunzip search kernel: a candidate count out of range");
+    uint16_t* drings = gu_rings_.reserve<uint16_t>(static_cast<uint64_t>(ncand) * inf::kWindow *
+                                                   sizeof(uint16_t));
+    inf::SpanRec* drecs = gu_recs_.reserve<inf::SpanRec>(ncand * sizeof(inf::SpanRec));
+    HIP_CHECK(modelx_inflate_measure_search(src, size, m.limit, dcand, ncand, drings, drecs,
+                                            hash_stream_));
+    HIP_CHECK(hipStreamSynchronize(hash_stream_));
+    std::vector<uint64_t> cand(ncand);
+    std::vector<inf::SpanRec> recs(ncand);
+    HIP_CHECK(hipMemcpy(cand.data(), dcand, ncand * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    HIP_CHECK(hipMemcpy(recs.data(), drecs, ncand * sizeof(inf::SpanRec), hipMemcpyDeviceToHost));
+    std::vector<inf::ChainLink> chain;
+    const inf::ChainResult cr = inf::walk_chain(
+        cand[0], m.limit, m.isize,
+        [&](uint64_t pos) -> const inf::SpanRec* {
+          auto it = std::lower_bound(cand.begin(), cand.end(), pos);
+          return it != cand.end() && *it == pos ? &recs[it - cand.begin()] : nullptr;
+        },
+        [&](uint64_t pos, const inf::SpanRec& rec, uint64_t out_offset) {
+          plan.spans.push_back({out_offset, rec.out_bytes, static_cast<uint32_t>(pos >> 4),
+                                static_cast<uint32_t>(pos & 15u)});
+          chain.push_back({static_cast<uint32_t>(std::lower_bound(cand.begin(), cand.end(), pos) -
+                                                 cand.begin()),
+                           static_cast<uint32_t>(rec.out_bytes & (inf::kWindow - 1))});
+        },
+        inf::search_end);
+    plan.status = cr.status;
+    plan.out_bytes = cr.out_bytes;
+    if (cr.status) {
+      plan.spans.clear();
+      return plan;
+    }
+    inf::ChainLink* dchain = gu_chain_.reserve<inf::ChainLink>(chain.size() * sizeof(inf::ChainLink));
+    uint8_t* dwin = gu_windows_.reserve<uint8_t>(chain.size() * static_cast<uint64_t>(inf::kWindow));
+    HIP_CHECK(hipMemcpyAsync(dchain, chain.data(), chain.size() * sizeof(inf::ChainLink),
+                             hipMemcpyHostToDevice, hash_stream_));
+    HIP_CHECK(modelx_inflate_windows(drings, dchain, static_cast<uint32_t>(chain.size()), dwin,
+                                     hash_stream_));
+    HIP_CHECK(hipStreamSynchronize(hash_stream_));
+    plan.generation = gu_generation_;
+    gu_window_spans_ = chain.size();
+    return plan;
+  }
+
   // Inflate the member at src_ptr into dst_ptr by the spans of `plan` (what
   // gunzip_plan_device returned for the same bytes), one emitting wave per
   // span, then the CRC-32 of the output in pieces joined here and compared
@@ -1120,7 +1197,8 @@ class GpuEngine {
   // a contiguous chain inside the member, a dst_cap below its size, an
   // output that overlaps the source, a span that does not decode to its
   // planned size, and a CRC-32 or ISIZE that differs; the kernel writes inside
-  // the planned spans only, whatever the plan holds.
+  // the planned spans only, whatever the plan holds. A search plan also raises
+  // once another plan call on this engine has replaced its windows.
   uint64_t gunzip_emit_device(uintptr_t src_ptr, uint64_t size, std::string_view plan_bytes,
                               uintptr_t dst_ptr, uint64_t dst_cap) {
     namespace inf = modelx::inflate;
@@ -1135,6 +1213,13 @@ class GpuEngine {
       throw std::runtime_error("gunzip_emit_device: the plan is not a list of spans");
     std::vector<inf::PlanSpan> spans(plan_bytes.size() / sizeof(inf::PlanSpan));
     std::memcpy(spans.data(), plan_bytes.data(), plan_bytes.size());
+    uint64_t generation = 0;  // nonzero: a search plan
+    if (spans[0].out_offset == kSearchPlanMagic) {
+      generation = spans[0].out_bytes;
+      spans.erase(spans.begin());
+      if (!generation || spans.empty())
+        throw std::runtime_error("gunzip_emit_device: the plan is not a list of spans");
+    }
     const uint64_t limit = size - deflate::kGzipTrailerBytes;
     uint64_t total = 0;
     for (const inf::PlanSpan& sp : spans) {
@@ -1150,6 +1235,9 @@ class GpuEngine {
     HIP_CHECK(hipSetDevice(device_));
     py::gil_scoped_release release;
     std::lock_guard<std::mutex> lk(gunzip_mu_);
+    if (generation && (generation != gu_generation_ || spans.size() != gu_window_spans_))
+      throw std::runtime_error("gunzip_emit_device: the search plan is stale: this engine has "
+                               "planned again since, and its windows are gone");
     const char* src = reinterpret_cast<const char*>(src_ptr);
     uint8_t tail[deflate::kGzipTrailerBytes];
     HIP_CHECK(hipMemcpy(tail, src + limit, sizeof tail, hipMemcpyDeviceToHost));
@@ -1157,15 +1245,21 @@ class GpuEngine {
       throw std::runtime_error("gunzip_emit_device: the plan's size is not the trailer's ISIZE");
     const uint32_t nspans = static_cast<uint32_t>(spans.size());
     const uint64_t pieces = (total + modelx::abi::kInflateCrcPiece - 1) / modelx::abi::kInflateCrcPiece;
-    inf::PlanSpan* dplan = gu_plan_.reserve<inf::PlanSpan>(plan_bytes.size());
+    const size_t span_bytes = spans.size() * sizeof(inf::PlanSpan);
+    inf::PlanSpan* dplan = gu_plan_.reserve<inf::PlanSpan>(span_bytes);
     uint32_t* derr = gu_err_.reserve<uint32_t>(sizeof(uint32_t));
     uint32_t* dcrc = gu_crc_.reserve<uint32_t>(std::max<uint64_t>(pieces, 1) * sizeof(uint32_t));
     uint32_t err = 0;
-    HIP_CHECK(hipMemcpyAsync(dplan, spans.data(), plan_bytes.size(), hipMemcpyHostToDevice,
+    HIP_CHECK(hipMemcpyAsync(dplan, spans.data(), span_bytes, hipMemcpyHostToDevice,
                              hash_stream_));
     HIP_CHECK(hipMemcpyAsync(derr, &err, sizeof err, hipMemcpyHostToDevice, hash_stream_));
-    HIP_CHECK(modelx_inflate_emit(src, size, limit, dplan, nspans,
-                                  reinterpret_cast<void*>(dst_ptr), derr, hash_stream_));
+    if (generation)
+      HIP_CHECK(modelx_inflate_emit_search(src, size, limit, dplan, nspans,
+                                           gu_windows_.reserve<uint8_t>(0),
+                                           reinterpret_cast<void*>(dst_ptr), derr, hash_stream_));
+    else
+      HIP_CHECK(modelx_inflate_emit(src, size, limit, dplan, nspans,
+                                    reinterpret_cast<void*>(dst_ptr), derr, hash_stream_));
     HIP_CHECK(modelx_crc32_pieces(reinterpret_cast<const void*>(dst_ptr), total, dcrc, hash_stream_));
     HIP_CHECK(hipStreamSynchronize(hash_stream_));
     HIP_CHECK(hipMemcpy(&err, derr, sizeof err, hipMemcpyDeviceToHost));
@@ -1956,7 +2050,21 @@ class GpuEngine {
   DeviceScratch gz_tokens_, gz_slots_, gz_out_, gz_addr_;
   std::mutex gunzip_mu_;  // guards the scratch of gunzip_plan_device and gunzip_emit_device
   DeviceScratch gu_counts_, gu_base_, gu_cand_, gu_recs_, gu_plan_, gu_err_, gu_crc_;
+  // search plans: the per-stride slots, the symbolic rings (64 KiB a
+  // candidate), the chain and its resolved windows (32 KiB a span), which
+  // belong to the plan call numbered gu_generation_
+  DeviceScratch gu_slots_, gu_rings_, gu_chain_, gu_windows_;
+  uint64_t gu_generation_ = 0;
+  size_t gu_window_spans_ = 0;  // windows resolved by the plan call gu_generation_
 };
+
+// The host model behind gzip_inflate_spans_host and gzip_inflate_plan_host.
+modelx::inflate::InflateResult gzip_inflate_host(std::string_view s, bool search) {
+  const uint8_t* data = reinterpret_cast<const uint8_t*>(s.data());
+  return search ? modelx::inflate::gzip_inflate_search(data, s.size(),
+                                                       modelx::abi::kInflateSearchStride)
+                : modelx::inflate::gzip_inflate_spans(data, s.size());
+}
 
 bool hip_available() {
   int n = 0;
@@ -2042,17 +2150,20 @@ PYBIND11_MODULE(_core, m) {
           py::arg("hist"), py::arg("maxbits"), py::arg("complete"))
       .def(
           "gunzip_plan_device",
-          [](GpuEngine& e, uintptr_t src_ptr, uint64_t size) {
-            auto plan = e.gunzip_plan_device(src_ptr, size);
+          [](GpuEngine& e, uintptr_t src_ptr, uint64_t size, bool search) {
+            auto plan = e.gunzip_plan_device(src_ptr, size, search);
             py::dict d;
             d["status"] = modelx::inflate::status_name(plan.status);
             d["out_bytes"] = plan.out_bytes;
             d["spans"] = plan.spans.size();
+            if (plan.generation && !plan.spans.empty())
+              plan.spans.insert(plan.spans.begin(),
+                                {GpuEngine::kSearchPlanMagic, plan.generation, 0, 0});
             d["plan"] = py::bytes(reinterpret_cast<const char*>(plan.spans.data()),
                                   plan.spans.size() * sizeof(modelx::inflate::PlanSpan));
             return d;
           },
-          py::arg("src_ptr"), py::arg("size"))
+          py::arg("src_ptr"), py::arg("size"), py::arg("search") = false)
       .def(
           "gunzip_emit_device",
           [](GpuEngine& e, uintptr_t src_ptr, uint64_t size, py::bytes plan, uintptr_t dst_ptr,
@@ -2248,30 +2359,30 @@ PYBIND11_MODULE(_core, m) {
   // equal in status, span count and bytes. An ineligible member gives its
   // status and no bytes. gzip_inflate_plan_host gives what the plan call
   // reports: status, out_bytes and the number of spans on the chain.
+  // search=True is the model of gunzip_plan_device(search=True): block search
+  // at kInflateSearchStride, symbolic windows, resolve.
   m.def(
       "gzip_inflate_spans_host",
-      [](py::bytes data) {
+      [](py::bytes data, bool search) {
         std::string_view s = data;
         modelx::inflate::InflateResult r;
         {
           py::gil_scoped_release release;
-          r = modelx::inflate::gzip_inflate_spans(reinterpret_cast<const uint8_t*>(s.data()),
-                                                  s.size());
+          r = gzip_inflate_host(s, search);
         }
         return py::make_tuple(modelx::inflate::status_name(r.status),
                               py::bytes(reinterpret_cast<const char*>(r.bytes.data()),
                                         r.bytes.size()));
       },
-      py::arg("data"));
+      py::arg("data"), py::arg("search") = false);
   m.def(
       "gzip_inflate_plan_host",
-      [](py::bytes data) {
+      [](py::bytes data, bool search) {
         std::string_view s = data;
         modelx::inflate::InflateResult r;
         {
           py::gil_scoped_release release;
-          r = modelx::inflate::gzip_inflate_spans(reinterpret_cast<const uint8_t*>(s.data()),
-                                                  s.size());
+          r = gzip_inflate_host(s, search);
         }
         py::dict d;
         d["status"] = modelx::inflate::status_name(r.status);
@@ -2279,7 +2390,7 @@ PYBIND11_MODULE(_core, m) {
         d["spans"] = r.spans;
         return d;
       },
-      py::arg("data"));
+      py::arg("data"), py::arg("search") = false);
   m.attr("GUNZIP_SPAN_MAX_CODED") = modelx::inflate::kSpanMaxCoded;
   // ChaCha20-Poly1305 sealed blobs on host bytes (aead_core.hpp): the model of
   // GpuEngine::aead_seal / aead_open and the CPU client's path. aead_open_host

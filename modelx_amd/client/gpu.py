@@ -183,12 +183,13 @@ class GpuClient:
     def __init__(self, registry: str, authorization: str = "", device: int = 0,
                  num_slots: int = DEFAULT_NUM_SLOTS, slot_bytes: int = DEFAULT_SLOT_BYTES,
                  num_conns: int = DEFAULT_NUM_CONNS, dedup: bool = False, cdc=False,
-                 key: Optional[bytes] = None, gpu_gunzip: bool = False):
+                 key: Optional[bytes] = None, gpu_gunzip=False):
         core = _core()
         # tar+gz directory blobs land through the engine like every other blob
         # and are inflated in HBM (core/hip/inflate.hip) instead of streamed
-        # through zlib on one core; see ``_gunzip_on_gpu``.
-        self.gpu_gunzip = gpu_gunzip
+        # through zlib on one core; see ``_gunzip_on_gpu``. "any" also takes
+        # the streams without sync markers that stock clients write.
+        self.gpu_gunzip = rules.check_gpu_gunzip(gpu_gunzip)
         # client-side encryption: the 32-byte key that ``push_from_gpu(...,
         # encrypt=True)`` seals blobs under and that pulls open sealed blobs
         # with (core/hip/aead.hip). It never leaves this process: each blob
@@ -1009,7 +1010,13 @@ class GpuClient:
         call finds the pieces and their sizes, the output is allocated, the
         emit call writes it and checks the CRC-32. That is the ``pull-gunzip``
         phase of ``last_stats`` (``bytes`` the archive, ``stored_bytes``,
-        ``spans``). Any other member (a stock gzip stream, several members) is
+        ``spans``). With ``gpu_gunzip="any"`` a member that plan calls
+        ``too-long`` or ``dependent`` (a stock gzip stream, ``Z_SYNC_FLUSH``) is
+        planned again with ``search=True``: block starts are searched for at a
+        fixed stride, every span decodes against a symbolic window and the
+        windows are resolved along the chain; that is ``pull-gunzip`` with
+        ``search=True``. Any other member (several members, or a stock stream
+        without ``"any"``) is
         inflated from the landed bytes by zlib on the host, recorded as
         ``pull-gunzip-cpu`` with the plan's ``status``; nothing is downloaded
         twice. While the member is inflated HBM holds it and its output; the
@@ -1019,11 +1026,17 @@ class GpuClient:
         t0 = time.monotonic()
         size = stored.numel()
         plan = self.engine.gunzip_plan_device(stored.data_ptr(), size)
+        extra = {}
+        if self.gpu_gunzip == "any" and plan["status"] in ("too-long", "dependent"):
+            again = self.engine.gunzip_plan_device(stored.data_ptr(), size, search=True)
+            if again["status"] == "ok":
+                plan, extra = again, {"search": True}
         if plan["status"] == "ok":
             out = self._device(plan["out_bytes"])
             self.engine.gunzip_emit_device(stored.data_ptr(), size, plan["plan"], out.data_ptr(),
                                            out.numel())
-            self._stat("pull-gunzip", out.numel(), t0, stored_bytes=size, spans=plan["spans"])
+            self._stat("pull-gunzip", out.numel(), t0, stored_bytes=size, spans=plan["spans"],
+                       **extra)
             return out
         try:
             raw = gzip.decompress(self.engine.read_device(stored.data_ptr(), size))

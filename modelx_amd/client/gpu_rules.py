@@ -283,6 +283,16 @@ def check_encrypt_key(key) -> None:
                              "the encryption key must be 32 bytes (or None)")
 
 
+def check_gpu_gunzip(value):
+    """The ``gpu_gunzip`` option of GpuClient: ``False``, ``True`` (members
+    that fall apart at sync markers) or ``"any"`` (also stock streams, by
+    block search); anything else is UNSUPPORTED."""
+    if value is False or value is True or value == "any":
+        return value
+    raise er.ModelxError(er.ErrCode.UNSUPPORTED,
+                         "gpu_gunzip must be False, True or \"any\"")
+
+
 def encrypt_segment(seg) -> int:
     """The ``encrypt_segment`` option of a push: ``None`` (the default) or a
     multiple of 1024 from 1024 to 16 MiB; anything else is UNSUPPORTED."""

@@ -17,7 +17,12 @@ without the kernels: ``zlib.decompressobj`` over the same member on one core,
 fed 1 MiB at a time as ``_stream_targz_to_device`` feeds it (no network, no
 staging copy).
 
+``--stock`` takes the members from ``zlib`` instead (one unflushed stream per
+payload and level, what stock clients write) and plans them with
+``search=True``: block search, symbolic windows, window chain.
+
     python tools/gunzip_micro.py [--mib 64] [--reps 5] [--warmup 1] [--cpu]
+                                 [--stock [--levels 1 6 9]]
 """
 import argparse
 import json
@@ -61,26 +66,39 @@ def main():
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--cpu", action="store_true")
+    ap.add_argument("--stock", action="store_true")
+    ap.add_argument("--levels", type=int, nargs="+", default=[1, 6, 9])
     args = ap.parse_args()
     if not _core.hip_available():
         raise SystemExit("gunzip_micro needs a GPU")
     eng = _core.GpuEngine(device=0, num_slots=2, slot_bytes=1 << 20, num_streams=1)
     result = {"reps": args.reps, "warmup": args.warmup, "runs": []}
+    search = {"search": True} if args.stock else {}
     for mib in args.mib:
         n = mib << 20
-        for name, src in payloads(n, "cuda:0").items():
+        cases = [(name, src, level) for name, src in payloads(n, "cuda:0").items()
+                 for level in (args.levels if args.stock else [None])]
+        for name, src, level in cases:
             torch.cuda.synchronize()  # the engine's stream does not order against torch's
-            bound = _core.gzip_compress_bound(n)
-            gz = torch.empty(bound, dtype=torch.uint8, device="cuda:0")
-            stored = eng.gzip_compress_device(src.data_ptr(), n, gz.data_ptr(), bound)
-            plan = eng.gunzip_plan_device(gz.data_ptr(), stored)
+            if args.stock:
+                co = zlib.compressobj(level, zlib.DEFLATED, 31)
+                member = co.compress(src.cpu().numpy().tobytes()) + co.flush()
+                stored = len(member)
+                gz = torch.frombuffer(bytearray(member + bytes(16)), dtype=torch.uint8).to("cuda:0")
+            else:
+                bound = _core.gzip_compress_bound(n)
+                gz = torch.empty(bound, dtype=torch.uint8, device="cuda:0")
+                stored = eng.gzip_compress_device(src.data_ptr(), n, gz.data_ptr(), bound)
+            plan = eng.gunzip_plan_device(gz.data_ptr(), stored, **search)
             assert plan["status"] == "ok" and plan["out_bytes"] == n, plan["status"]
             out = torch.zeros(n, dtype=torch.uint8, device="cuda:0")
             torch.cuda.synchronize()
             eng.gunzip_emit_device(gz.data_ptr(), stored, plan["plan"], out.data_ptr(), n)
             assert torch.equal(out, src), "the output is not the source"
-            t_plan = timed(lambda: eng.gunzip_plan_device(gz.data_ptr(), stored),
+            t_plan = timed(lambda: eng.gunzip_plan_device(gz.data_ptr(), stored, **search),
                            args.warmup, args.reps)
+            if args.stock:  # the timed plan calls made the emit's plan stale
+                plan = eng.gunzip_plan_device(gz.data_ptr(), stored, **search)
             t_emit = timed(lambda: eng.gunzip_emit_device(gz.data_ptr(), stored, plan["plan"],
                                                           out.data_ptr(), n),
                            args.warmup, args.reps)
@@ -91,6 +109,8 @@ def main():
                    "emit_median_ms": statistics.median(t_emit) * 1e3,
                    "emit_min_ms": min(t_emit) * 1e3, "emit_max_ms": max(t_emit) * 1e3,
                    "gib_s": gib / both}
+            if args.stock:
+                run["level"] = level
             if args.cpu:
                 member = gz[:stored].cpu().numpy().tobytes()
                 inflater = zlib.decompressobj(16 + zlib.MAX_WBITS)
